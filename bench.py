@@ -8,13 +8,19 @@ reference of BASELINE.json configs[1] (1000 long + 9000 short flanks, l_pac 6,51
 
 Boundary of `value`: packed read batches in pinned host memory in -> result records in host memory out
 (fq_packed_prefetch + fq_align_packed: the 48 bytes of filter keys per pair cross PCIe for every pair, the reads themselves
-only for surviving pairs; the next batch's upload runs under this batch's kernels).  `resident_value` is the same workload
-with the ASCII batch already in HBM (fq_batch_upload outside, fq_align_resident inside): the device-side rate.  `ontarget`
-is a short second leg on the on-target-only mix, where the Occ-lookup (gap search) kernel fills the device.  Multi-GPU:
-one process per GPU, reads shard by batch, no data-path collective ("weak" scaling); the only
-collectives are the barrier and the MAX over ranks of the elapsed time.
+only for surviving pairs; the next batch's upload runs under this batch's kernels).  Multi-GPU: one process per GPU, reads
+shard by batch, no data-path collective ("weak" scaling); the only collectives are the barrier and the MAX over ranks of the
+elapsed time.
+
+A plain run sets up, warms up, times --steps steps and prints one JSON line (`value`, `ms_per_step`, and the per-kernel figures
+of the timed steps' own counters).  --full adds the other legs: `resident_value` (the same workload with the ASCII batch
+already in HBM: fq_batch_upload outside, fq_align_resident inside), `ontarget` (the on-target-only mix, where the Occ-lookup
+(gap search) kernel fills the device), `host_budget`, the kernels alone after the timed steps (`roofline.solo_*`), the
+multi-GPU `gather` and `stream_shard`, `front_end` and `cpu_baseline`.  --dump-outputs DIR writes what the last timed step
+returned (result_arrays) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared array for array.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -57,7 +63,7 @@ def host_budget_child(args):
     hb_cpus = 2
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(max(4, min(args.steps, 16))), "--warmup", str(max(2, min(args.warmup, 8))),
            "--pairs", str(args.pairs), "--ctxs", str(args.ctxs), "--markers", str(args.markers), "--mix", args.mix, "--read-len", str(args.read_len),
-           "--boundary", args.boundary, "--host-cpus", str(hb_cpus), "--no-resident", "--no-front-end", "--no-cpu-baseline", "--no-host-budget",
+           "--boundary", args.boundary, "--host-cpus", str(hb_cpus), "--full", "--no-resident", "--no-front-end", "--no-cpu-baseline", "--no-host-budget",
            "--ontarget-tput-ctxs", "0", "--workdir", args.workdir] + (["--no-ontarget"] if args.no_ontarget else []) + (["--tune", args.tune] if args.tune else [])
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     t0 = time.perf_counter()
@@ -70,6 +76,120 @@ def host_budget_child(args):
     else:
         hb["error"] = run.stderr.decode(errors="replace")[-500:]
     return hb
+
+
+def stream_run_keep_last(api, aligners, batches, n_calls, first):
+    """fq_stream_run as api.stream_run(..., prefetch_beyond=True) calls it, with a callback that copies each stream's last fq_result_batch_t
+    (counts and pointers into the context's storage, valid until the next call on that context).  Returns (survivors per stream, results)."""
+    import ctypes as C
+    n = len(aligners)
+    last = [api.ResultBatch() for _ in range(n)]
+
+    def cb(_user, stream, call, res):
+        if call == n_calls - 1:
+            C.memmove(C.addressof(last[stream]), res, C.sizeof(api.ResultBatch))
+        return 0
+    fn = api.STREAM_CALL(cb)
+    L = aligners[0].L
+    ctxs = (C.c_void_p * n)(*[al.h for al in aligners])
+    rows = [(C.POINTER(api.PackedBatch) * len(bs))(*[b.p for b in bs]) for bs in batches]
+    tab = (C.POINTER(C.POINTER(api.PackedBatch)) * n)(*[C.cast(r, C.POINTER(C.POINTER(api.PackedBatch))) for r in rows])
+    nb = (C.c_int32 * n)(*[len(bs) for bs in batches])
+    fst = (C.c_int32 * n)(*first)
+    surv = (C.c_int64 * n)()
+    rc = L.fq_stream_run(ctxs, n, tab, nb, fst, n_calls, 1, fn, None, surv)
+    if rc:
+        raise api.FastquickError("fq_stream_run failed: %d" % rc)
+    return list(surv), last
+
+
+REC_F64 = ("pos", "sa", "c1", "c2")
+REC_F32 = ("score", "len", "full_len", "clip_len", "type", "strand", "filtered", "extra_flag", "n_mm", "n_gapo", "n_gape", "mapQ", "seQ",
+           "revived", "nm", "n_cigar", "n_multi")
+DUMP_BUDGET = 60 << 20          # bytes of .npy payload at most (--dump-outputs: 64 MB in all)
+
+
+def result_arrays(api, results, seed=0):
+    """What the callers of the timed calls received (one fq_result_batch_t per stream) as float arrays, storage offsets replaced by the
+    contents they point at: per stream the counts and insert-size estimates; per surviving pair its stream, index and two records; the
+    CIGAR entries, MD strings and XA hits of the records concatenated in record order.  Where all of it would exceed DUMP_BUDGET, a seeded
+    sample of the surviving pairs (the same pairs for the same outputs).  An array with no element is left out: the records' counts
+    (rec_n_cigar, rec_md_len, rec_n_multi) say that there is nothing, e.g. no XA hit in the step."""
+    import ctypes as C
+    import numpy as np
+
+    def struct_dtype(st):
+        names = [f for f, _ in st._fields_ if f != "pad"]
+        fmt = {C.c_uint32: "<u4", C.c_int32: "<i4", C.c_uint16: "<u2", C.c_uint8: "u1"}
+        return np.dtype({"names": names, "formats": [fmt[t] for f, t in st._fields_ if f != "pad"],
+                         "offsets": [getattr(st, f).offset for f in names], "itemsize": C.sizeof(st)})
+
+    def raw(ptr, dtype, count):
+        if count <= 0:
+            return np.zeros(0, dtype)
+        return np.frombuffer(C.string_at(C.cast(ptr, C.c_void_p).value, count * dtype.itemsize), dtype).copy()
+    rec_dt, multi_dt = struct_dtype(api.Result), struct_dtype(api.Multi)
+    isz = lambda i: [i.avg, i.std, i.ap_prior, i.low, i.high, i.high_bayesian]      # noqa: E731
+    streams = []
+    for rb in results:
+        n = int(rb.n_survivors)
+        if n > 0 and not rb.rec:
+            raise RuntimeError("the result arrays stayed on the device (FQ_EMIT_DEVICE_ONLY): nothing to dump")
+        rec = raw(rb.rec, rec_dt, 2 * n)
+        multi_n = int((rec["multi_off"].astype(np.int64) + rec["n_multi"])[rec["n_multi"] > 0].max(initial=0)) if n else 0
+        multi = raw(rb.multi, multi_dt, multi_n)
+        cig_n = max(int((rec["cigar_off"].astype(np.int64) + rec["n_cigar"])[rec["n_cigar"] > 0].max(initial=0)),
+                    int((multi["cigar_off"].astype(np.int64) + multi["n_cigar"])[multi["n_cigar"] > 0].max(initial=0)) if multi_n else 0)
+        md_base = C.cast(rb.md, C.c_void_p).value
+        md = [C.string_at(md_base + int(o)) if o != 0xffffffff and md_base else None for o in rec["md_off"]]
+        streams.append({"n": n, "pair_idx": raw(rb.pair_idx, np.dtype("<i4"), n), "rec": rec, "multi": multi, "md": md,
+                        "cigar": raw(rb.cigar, np.dtype("<u2"), cig_n),
+                        "counts": [rb.n_pairs, n, rb.n_both_filtered, rb.n_both_unmapped, rb.n_bases, rb.n_sub],
+                        "isize": isz(rb.isize), "isize_sub": [isz(rb.isize_sub[k]) for k in range(rb.n_sub)] if rb.isize_sub else []})
+    # bytes per surviving pair in the files below: its two records, their CIGAR entries, MD strings and XA hits (with theirs)
+    cost = []
+    for s in streams:
+        r, m = s["rec"], s["multi"]
+        var = 4 * r["n_cigar"].astype(np.int64) + np.array([4 * (len(x) if x is not None else 0) for x in s["md"]], np.int64)
+        for i in np.nonzero(r["n_multi"])[0]:
+            hits = m[r["multi_off"][i]:r["multi_off"][i] + r["n_multi"][i]]
+            var[i] += 24 * len(hits) + 4 * int(hits["n_cigar"].sum())
+        cost.append(12 + 2 * (8 * len(REC_F64) + 4 * len(REC_F32) + 4) + var.reshape(-1, 2).sum(axis=1))
+    cost = np.concatenate(cost) if cost else np.zeros(0, np.int64)
+    keep = np.arange(len(cost))
+    if cost.sum() > DUMP_BUDGET:
+        order = np.random.default_rng(seed).permutation(len(cost))
+        keep = np.sort(order[np.cumsum(cost[order]) <= DUMP_BUDGET])
+    def ragged(src, off, cnt):        # src[off[i]:off[i] + cnt[i]] for every i, concatenated
+        cnt = cnt.astype(np.int64)
+        starts = np.repeat(off.astype(np.int64) - (np.cumsum(cnt) - cnt), cnt)
+        return src[starts + np.arange(int(cnt.sum()), dtype=np.int64)]
+    base = np.cumsum([0] + [s["n"] for s in streams])
+    parts = {}
+    for si, s in enumerate(streams):
+        p = keep[(keep >= base[si]) & (keep < base[si + 1])] - base[si]
+        ri = np.stack([2 * p, 2 * p + 1], axis=1).ravel()
+        r = s["rec"][ri]
+        hits = ragged(s["multi"], r["multi_off"], r["n_multi"])
+        md = [s["md"][i] for i in ri]
+        got = {"pair_stream": np.full(len(p), si), "pair_idx": s["pair_idx"][p],
+               "cigar": ragged(s["cigar"], r["cigar_off"], r["n_cigar"]),
+               "rec_md_len": np.array([-1 if x is None else len(x) for x in md]),
+               "md": np.frombuffer(b"".join(x or b"" for x in md), np.uint8),
+               "multi_cigar": ragged(s["cigar"], hits["cigar_off"], hits["n_cigar"])}
+        got.update({"rec_" + f: r[f] for f in REC_F64 + REC_F32})
+        got.update({"multi_" + f: hits[f] for f in ("pos", "n_cigar", "gap", "mm", "strand")})
+        for k, v in got.items():
+            parts.setdefault(k, []).append(v)
+    out = {"counts": np.array([s["counts"] for s in streams], np.float64).reshape(-1, 6),
+           "isize": np.array([s["isize"] for s in streams], np.float64).reshape(-1, 6),
+           "isize_sub": np.array([x for s in streams for x in s["isize_sub"]], np.float64).reshape(-1, 6)}
+    for k, v in parts.items():
+        wide = k in ("pair_idx", "multi_pos") or k[4:] in REC_F64
+        a = np.concatenate(v).astype(np.float64 if wide else np.float32)
+        out[k] = a.reshape(-1, 2) if k.startswith("rec_") else a
+    out = {k: a for k, a in out.items() if a.size}
+    return out, {"surviving_pairs": int(len(cost)), "pairs_written": int(len(keep))}
 
 
 def main() -> None:
@@ -112,6 +232,11 @@ def main() -> None:
     ap.add_argument("--host-cpus", type=int, default=0, help="run inside a host budget of this many CPUs: the process is pinned to them (sched_setaffinity) and the library told its share "
                     "(FASTQUICK_HOST_CPUS) before anything touches the device; 0: the whole allowance.  The default run times itself once more this way (host_budget)")
     ap.add_argument("--no-host-budget", action="store_true", help="skip the host_budget leg (the run repeated on 2 CPUs)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline figure, each leg subject to its --no-* option: host_budget, the kernels "
+                    "alone after the timed steps (roofline.solo_*), the multi-GPU gather and stream_shard, resident, ontarget, front_end, cpu_baseline.  "
+                    "Without it a run sets up, warms up, times --steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what their last step returned to its callers "
+                    "(every stream's fq_result_batch_t; rank 0) as DIR/<name>.npy, float32 / float64, %d MB at most" % (DUMP_BUDGET >> 20))
     args = ap.parse_args()
     if args.host_cpus > 0:
         allowed = sorted(os.sched_getaffinity(0))
@@ -124,7 +249,7 @@ def main() -> None:
     hb_result = None
     # (under a profiler the preloaded library has initialised the GPU already and a child would write into the same output directory: no host-budget leg there)
     profiled = "rocprof" in os.environ.get("LD_PRELOAD", "") or any(k.startswith(("ROCPROFILER_", "ROCPROF_", "ROCP_")) for k in os.environ)
-    if args.host_cpus == 0 and not args.no_host_budget and not profiled and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
+    if args.full and args.host_cpus == 0 and not args.no_host_budget and not profiled and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         hb_result = host_budget_child(args)          # (before anything here touches the device)
 
     import numpy as np
@@ -135,7 +260,7 @@ def main() -> None:
     from fastquick_amd import dist as fqd
     api.load_library().fq_runtime_configure(20, 1)   # hardware queues for the contexts' streams, sleeping waits (include/fastquick_amd.h)
     rank, local_rank, world = fqd.init("nccl")      # RCCL; one process per GPU
-    if world > 1 and args.stream_shard > 0 and args.mix == "wgs":
+    if args.full and world > 1 and args.stream_shard > 0 and args.mix == "wgs":
         # the gloo group the stream tokens of the stream-shard leg travel over: new_group is a collective, so every rank creates it HERE,
         # unconditionally and before anything rank-specific can fail (created inside that leg's try block, a rank that failed before it
         # left the others waiting in the collective)
@@ -207,10 +332,11 @@ def main() -> None:
                     agg[k] = [a + b for a, b in zip(agg[k], v)] if isinstance(v, list) else (max(agg[k], v) if k.startswith("max_") else agg[k] + v)
         return agg
 
-    def run_leg(mix, pairs, n_ctx, steps, warmup, boundary, seed0, keep=False, max_distinct=4):
+    def run_leg(mix, pairs, n_ctx, steps, warmup, boundary, seed0, keep=False, max_distinct=4, capture=False):
         """One measured leg: n_ctx contexts (independent FASTQ streams), each driven by its own host thread; a step = one call
         of `pairs` pairs on every context.  boundary "host": every call takes a packed batch from pinned host memory (the next
-        one prefetched under it) and returns records in host memory; "resident": the ASCII batch was uploaded before."""
+        one prefetched under it) and returns records in host memory; "resident": the ASCII batch was uploaded before.
+        capture: the last timed step's results as arrays (result_arrays), taken after the timed region."""
         on_frac = 1.0 if mix == "ontarget" else ref.l_pac / 3.1e9
         # distinct host batches are large (2.7 GB of ASCII each at the default size): at most four per rank, taken round-robin
         n_distinct = min(n_ctx, max_distinct) if boundary == "resident" else min(max(n_ctx, 2), max_distinct)
@@ -228,13 +354,17 @@ def main() -> None:
 
         t_run0 = [0.0]
         cur_of = [c % n_distinct for c in range(n_ctx)]     # each context walks the batches round-robin, across run_steps calls
+        last = []
 
-        def run_steps(k_steps):
+        def run_steps(k_steps, keep_last=False):
             if boundary == "host":
                 # the streams' driver loops (prefetch the next batch, align this one) run inside the library: fq_stream_run, one library thread per
                 # stream asleep while the device works; no Python thread per stream
                 t_run0[0] = time.perf_counter()
-                surv = api.stream_run(ctxs, [packs] * n_ctx, k_steps, first=list(cur_of), prefetch_beyond=True)
+                if keep_last:
+                    surv, last[:] = stream_run_keep_last(api, ctxs, [packs] * n_ctx, k_steps, list(cur_of))
+                else:
+                    surv = api.stream_run(ctxs, [packs] * n_ctx, k_steps, first=list(cur_of), prefetch_beyond=True)
                 for c in range(n_ctx):
                     cur_of[c] = (cur_of[c] + k_steps) % n_distinct
                 return sum(surv)
@@ -256,6 +386,7 @@ def main() -> None:
                 t.join()
             if errs:
                 raise errs[0]
+            last[:] = [al.result for al in ctxs]
             return sum(recs)
 
         run_steps(1)                    # set-up: the first call of a context sizes its device buffers
@@ -265,15 +396,17 @@ def main() -> None:
             al.reset_stats()
         sync_all()
         t0 = time.perf_counter()
-        n_records = run_steps(steps)
+        n_records = run_steps(steps, keep_last=capture)
         sync_all()
         elapsed = fqd.max_over_ranks(time.perf_counter() - t0)
         agg = sum_stats(ctxs)
         calls = steps * n_ctx
         leg = {"elapsed": elapsed, "calls": calls, "agg": agg, "n_records": n_records, "on_frac": on_frac, "pairs": pairs, "n_ctx": n_ctx, "n_distinct": n_distinct,
                "value": pairs * calls * world / elapsed}
+        if capture:       # (before any other call on the contexts: their storage holds the last step's results until then)
+            leg["outputs"] = result_arrays(api, last)
         # the same kernels alone on the device (one stream, after the timed region): launch duration without other streams' kernels
-        if n_ctx > 1:
+        if args.full and n_ctx > 1:
             ctxs[0].reset_stats()
             for _ in range(3):
                 if boundary == "host":
@@ -332,7 +465,15 @@ def main() -> None:
 
     # ---- the headline leg ---------------------------------------------------------------------------------------------
     n_ctx = max(1, args.ctxs)
-    main_leg = run_leg(args.mix, args.pairs, n_ctx, args.steps, args.warmup, args.boundary, 1000, keep=True)
+    main_leg = run_leg(args.mix, args.pairs, n_ctx, args.steps, args.warmup, args.boundary, 1000, keep=True, capture=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        arrays, counts = main_leg.pop("outputs")
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+        print("bench.py: %d arrays (%.1f MB) of the last timed step in %s: %d of %d surviving pairs" % (len(arrays), sum(a.nbytes for a in arrays.values()) / 1e6,
+              args.dump_outputs, counts["pairs_written"], counts["surviving_pairs"]), file=sys.stderr)
     elapsed, calls, agg = main_leg["elapsed"], main_leg["calls"], main_leg["agg"]
     pairs_total = args.pairs * calls
     kms = agg["kernel_ms"]
@@ -420,7 +561,7 @@ def main() -> None:
     #      Whether to gather is decided from the run's arguments, the same on every rank (a per-rank decision could leave some
     #      ranks outside the collective).
     ctxs = main_leg["ctxs"]
-    if args.mix == "wgs":
+    if args.full and args.mix == "wgs":
         last = ctxs[0].result
         parts = fqd.gather_bytes_to_rank0(ctxs[0].sam_text())
         tot = fqd.sum_counters({"pairs": int(last.n_pairs), "survivor_pairs": int(last.n_survivors), "both_filtered": int(last.n_both_filtered),
@@ -435,7 +576,7 @@ def main() -> None:
     # ---- the other partitioning: ONE stream over the ranks, sharded by reference batch; the stream state (drand48, last_ii,
     #      (k,l) cache) goes from the owner of batch b to the owner of b + 1 around the short order-dependent part of each call.  No
     #      data-path collective: point-to-point tokens of a few hundred bytes.  Reported beside `value`, never instead of it.
-    if world > 1 and args.stream_shard > 0 and args.mix == "wgs":
+    if args.full and world > 1 and args.stream_shard > 0 and args.mix == "wgs":
         Bs = 262144
         nb = args.stream_shard * world
         shard_err, el, recs, sp, al = "", 0.0, 0, {}, None
@@ -468,14 +609,14 @@ def main() -> None:
         if al is not None:
             al.close()
     cpu_seq = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_seq = cpu_batch.seq if cpu_batch.seq is not None else make_batch(args.pairs, 1000 + 17 * rank, main_leg["on_frac"]).seq
     for p in main_leg["packs"] or []:
         p.free()
     main_leg["ctxs"] = main_leg["packs"] = None
 
     # ---- the device-side rate of the same workload (inputs already in HBM), fewer steps --------------------------------------------
-    if args.boundary == "host" and not args.no_resident:
+    if args.full and args.boundary == "host" and not args.no_resident:
         rs = max(2, args.steps // 4)
         leg = run_leg(args.mix, args.pairs, n_ctx, rs, max(1, min(args.warmup, 2)), "resident", 1000)
         out["resident_value"] = round(leg["value"], 1)
@@ -484,7 +625,7 @@ def main() -> None:
 
     # ---- on-target leg: every pair from a marker flank, one device-filling search launch per call (the >= 40 % criterion of
     #      BASELINE.json is about this kernel on this mix) -------------------------------------------------------------------------------
-    if args.mix == "wgs" and not args.no_ontarget:
+    if args.full and args.mix == "wgs" and not args.no_ontarget:
         if args.ontarget_pairs <= 0:
             args.ontarget_pairs = args.pairs
         leg = run_leg("ontarget", args.ontarget_pairs, args.ontarget_ctxs, args.ontarget_steps, 1, args.boundary, 3000, max_distinct=2)
@@ -546,7 +687,7 @@ def main() -> None:
     #   pack_pairs_per_s              fq_pack_reads_into on the headline call's batch (ASCII rows -> packed batch in reused pinned storage)
     #   tokenise_inflate_pairs_per_s  two BGZF FASTQ files -> ASCII rows (fq_fastq_read: member-parallel inflate + tokeniser), both files at once
     #   cli_e2e_pairs_per_s           the command line on those files: FASTQ -> SAM text, whole-process wall time (index staging included)
-    if rank == 0 and world == 1 and not args.no_front_end:
+    if args.full and rank == 0 and world == 1 and not args.no_front_end:
         if cpu_batch.seq is None:     # (the headline leg dropped its ASCII rows once they were packed)
             cpu_batch.seq = cpu_seq if cpu_seq is not None else make_batch(args.pairs, 1000 + 17 * rank, main_leg["on_frac"]).seq
         cores = os.cpu_count() or 1

@@ -28,7 +28,7 @@ case $WHAT in
 timeline)
   N=${1:?ctxs}; shift
   rm -rf $O/${TAG}_tl$N
-  timeout 900 rocprofv3 --kernel-trace --output-format csv -d $O/${TAG}_tl$N -o p -- python3 $R/bench.py --mix ontarget --pairs 4194304 --ctxs $N --steps 6 --warmup 2 $Q "$@" > $O/${TAG}_tl$N.json 2> $O/${TAG}_tl$N.err
+  timeout 900 rocprofv3 --kernel-trace --output-format csv -d $O/${TAG}_tl$N -o p -- python3 $R/bench.py --full --mix ontarget --pairs 4194304 --ctxs $N --steps 6 --warmup 2 $Q "$@" > $O/${TAG}_tl$N.json 2> $O/${TAG}_tl$N.err
   python3 - <<PY > $O/${TAG}_timeline_$N.txt
 import csv, glob, json, collections
 f = glob.glob("$O/${TAG}_tl$N/**/*kernel_trace.csv", recursive=True)[0]
@@ -141,7 +141,7 @@ reader)
   cd $R
   : > $O/${TAG}_reader.txt
   for z in 1 0; do
-    FASTQUICK_ZLIB_INFLATE=$z timeout 1200 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-resident --no-ontarget > $O/${TAG}_rd_$z.json 2> $O/${TAG}_rd_$z.err
+    FASTQUICK_ZLIB_INFLATE=$z timeout 1200 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-resident --no-ontarget > $O/${TAG}_rd_$z.json 2> $O/${TAG}_rd_$z.err
     python3 -c "
 import json
 d = json.loads(open('$O/${TAG}_rd_$z.json').read().strip().splitlines()[-1])

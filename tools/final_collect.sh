@@ -8,16 +8,16 @@ mkdir -p $O
 cd $R
 timeout 1800 python -m pytest tests -x -q -m gpu 2>&1 | tail -3 > $O/${TAG}_gpu_tests.txt
 python -c 'import __graft_entry__ as g; g.smoke(); print("smoke ok")' > $O/${TAG}_smoke.txt 2>&1
-( time timeout 1200 python bench.py > $O/${TAG}_default_bench.json 2> $O/${TAG}_default_bench.err ) 2> $O/${TAG}_default_bench.time
+( time timeout 1200 python bench.py --full > $O/${TAG}_default_bench.json 2> $O/${TAG}_default_bench.err ) 2> $O/${TAG}_default_bench.time
 bash tools/experiment.sh trace $TAG 4194304 > /dev/null
 bash tools/experiment.sh timeline $TAG 2 > /dev/null
 Q="--no-cpu-baseline --no-resident --no-ontarget --no-front-end --no-host-budget"
-bash tools/experiment.sh stats $TAG wgs --steps 20 --warmup 5 --no-front-end --no-cpu-baseline > /dev/null
-bash tools/experiment.sh stats $TAG wgs_mainleg --steps 20 --warmup 5 $Q > /dev/null
+bash tools/experiment.sh stats $TAG wgs --full --steps 20 --warmup 5 --no-front-end --no-cpu-baseline > /dev/null
+bash tools/experiment.sh stats $TAG wgs_mainleg --full --steps 20 --warmup 5 $Q > /dev/null
 bash tools/experiment.sh stats $TAG ont4m --mix ontarget --pairs 4194304 --ctxs 1 --steps 3 --warmup 1 $Q > /dev/null
 bash tools/experiment.sh stats $TAG ont --mix ontarget --pairs 1048576 --ctxs 1 --steps 3 --warmup 1 $Q > /dev/null
-bash tools/experiment.sh stats $TAG 100k --markers 100000 --steps 6 --warmup 2 --no-cpu-baseline --no-resident --no-front-end --ontarget-tput-ctxs 0 > /dev/null
-bash tools/experiment.sh stats $TAG 76bp_ontarget --mix ontarget --read-len 76 --pairs 1048576 --ctxs 2 --steps 3 --warmup 1 $Q > /dev/null
+bash tools/experiment.sh stats $TAG 100k --full --markers 100000 --steps 6 --warmup 2 --no-cpu-baseline --no-resident --no-front-end --ontarget-tput-ctxs 0 > /dev/null
+bash tools/experiment.sh stats $TAG 76bp_ontarget --full --mix ontarget --read-len 76 --pairs 1048576 --ctxs 2 --steps 3 --warmup 1 $Q > /dev/null
 cd /tmp && export TMPDIR=/tmp
 pmc() {   # name, counter, bench args...
   local name=$1 ctr=$2; shift; shift
@@ -25,14 +25,14 @@ pmc() {   # name, counter, bench args...
   find $O/${TAG}_pmc_${name}_$ctr -name '*kernel_trace.csv' -delete
 }
 for c in FETCH_SIZE WRITE_SIZE; do
-  pmc wgs $c --steps 4 --warmup 2 $Q
+  pmc wgs $c --full --steps 4 --warmup 2 $Q
   pmc ont $c --mix ontarget --pairs 1048576 --ctxs 1 --steps 2 --warmup 1 $Q
   pmc ont4m $c --mix ontarget --pairs 4194304 --ctxs 1 --steps 2 --warmup 1 $Q
 done
 # ---- the device front end: kernel durations of a 67 M-pair BGZF stream (rocprofv3 --kernel-trace --stats; kernels one after the other so that each
 #      duration is the kernel's own, then the product's overlapped order), the command line's time marks, the member decoder's SQ counters
 cd $R
-python bench.py --steps 2 --warmup 1 --no-resident --no-ontarget --no-cpu-baseline --front-end-copies 0 --ontarget-tput-ctxs 0 --no-host-budget --workdir /tmp/fq_bench > /dev/null 2>&1
+python bench.py --full --steps 2 --warmup 1 --no-resident --no-ontarget --no-cpu-baseline --front-end-copies 0 --ontarget-tput-ctxs 0 --no-host-budget --workdir /tmp/fq_bench > /dev/null 2>&1
 bash tools/cli_trace.sh /tmp/fq_bench 64 qc > $O/${TAG}_cli_trace.txt 2>&1
 F=/tmp/fq_bench/front_end
 cd /tmp && export TMPDIR=/tmp

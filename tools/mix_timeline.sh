@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out; TAG=${1:?tag}; shift; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/${TAG}_mtl
-timeout 900 rocprofv3 --kernel-trace --output-format csv -d $O/${TAG}_mtl -o p -- python3 $R/bench.py "$@" --no-cpu-baseline --no-resident --no-ontarget --no-front-end > $O/${TAG}_mtl.json 2> $O/${TAG}_mtl.err
+timeout 900 rocprofv3 --kernel-trace --output-format csv -d $O/${TAG}_mtl -o p -- python3 $R/bench.py --full "$@" --no-cpu-baseline --no-resident --no-ontarget --no-front-end > $O/${TAG}_mtl.json 2> $O/${TAG}_mtl.err
 python3 - "$@" <<PY > $O/${TAG}_mix_timeline.txt
 import csv, glob, json, collections, sys
 f = glob.glob("$O/${TAG}_mtl/**/*kernel_trace.csv", recursive=True)[0]
