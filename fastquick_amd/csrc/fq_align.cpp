@@ -223,6 +223,14 @@ struct FqKnobs {   // experiment / test knobs (fq_ctx_set_tuning); defaults are 
   int trace = 0;
 };
 
+struct SearchBufs {   // the per-launch buffers of the search stage (stageA_search)
+  DevBuf<int32_t> work;                                                                          // the launch's reads (search indices)
+  DevBuf<uint32_t> wfull; DevBuf<FqPos> prec; DevBuf<FqGapWork> winfo; DevBuf<uint8_t> bid_end;  // k_width: exact widths, position records, a read's start-up word, the ends' lower bounds
+  DevBuf<int32_t> order; DevBuf<uint32_t> order_cnt;                                             // the order the search takes the reads in, and its counts per key
+  DevBuf<FqAln> aln; DevBuf<uint32_t> naln, status;                                              // per read: its hits, their number, 0 = settled
+  DevBuf<uint32_t> queue, heads; DevBuf<FqEntry> pool;                                           // the persistent lanes' work queue, bucket heads and stack pools
+};
+
 struct fq_ctx {
   FqWorkPool pool;                     // the workers of this context's host phases (parallel_chunks on the calling thread)
   const fq_index *ix = nullptr;
@@ -273,24 +281,12 @@ struct fq_ctx {
   DevBuf<uint16_t> d_blen;
   // device-resident reads (ASCII rows the kernels after the filter read): whole batch (ASCII input) or survivors only (packed)
   DevBuf<uint8_t> d_seq, d_qual, d_filtered, d_maxdiff;
-  DevBuf<FqGapWork> d_winfo;
   DevBuf<int32_t> d_len, d_len_trim, d_read_list, d_sidx, d_pair_list, d_counts;
   DevBuf<uint64_t> d_counters;
   std::vector<uint64_t> h_counters;   // (its stripes, as read back)
-  DevBuf<uint32_t> d_queue;
-  // search workspaces
-  DevBuf<int32_t> d_work;
-  DevBuf<uint32_t> d_heads, d_naln, d_status;
-  DevBuf<uint32_t> d_wfull;
-  DevBuf<FqPos> d_prec;
-  DevBuf<uint8_t> d_bid_end;
-  DevBuf<int32_t> d_order;
-  DevBuf<uint32_t> d_order_cnt;
-  DevBuf<FqEntry> d_pool;
-  // second set for the search rounds that run beside the first round of a large call (stageA_search)
-  DevBuf<FqGapWork> d_winfo2; DevBuf<uint32_t> d_queue2, d_heads2, d_naln2, d_status2, d_wfull2, d_order_cnt2, d_cnt2; DevBuf<int32_t> d_work2, d_order2;
-  DevBuf<FqPos> d_prec2; DevBuf<uint8_t> d_bid_end2; DevBuf<FqEntry> d_pool2; DevBuf<FqAln> d_aln2;
-  DevBuf<FqAln> d_aln;
+  // search workspaces: [0] every launch's, [1] the second rounds' that run beside the first round of a large call (search_pipelined) and the reads each segment leaves them
+  SearchBufs sb[2];
+  DevBuf<uint32_t> d_seg_cnt;
   DevBuf<FqAln> d_hits;                   // the hit lists of the call, every launch's behind the earlier ones'; by search index: d_aoff / d_an
   DevBuf<uint64_t> d_aoff; DevBuf<uint32_t> d_an;
   DevBuf<uint64_t> d_off;
@@ -427,7 +423,7 @@ extern "C" int fq_ctx_create(const fq_index_t *ix, const fq_opts_t *opts, int32_
   if (const char *e = getenv("FASTQUICK_CTX_TRACE")) c->kn.trace = atoi(e);     // per-stage wall times of every call on stderr (as the tuning key `trace`)
   c->dev = fqdev::state_create(ix->device);
   if (!c->dev || fqdev::bind(c->dev)) return FQ_ENODEV;
-  if (!c->d_maxdiff.ensure(FQ_LMAX + 2) || !c->d_counters.ensure(FQ_C_STRIPES * FQ_C_STRIDE) || !c->d_counts.ensure(4) || !c->d_queue.ensure(4) || !c->d_glogn.ensure(256)) return FQ_ENOMEM;
+  if (!c->d_maxdiff.ensure(FQ_LMAX + 2) || !c->d_counters.ensure(FQ_C_STRIPES * FQ_C_STRIDE) || !c->d_counts.ensure(4) || !c->sb[0].queue.ensure(4) || !c->d_glogn.ensure(256)) return FQ_ENOMEM;
   if (fqdev::h2d(c->d_maxdiff.p, c->maxdiff_lut, FQ_LMAX + 2) || fqdev::h2d(c->d_glogn.p, c->g_log_n, 256 * 4) || fqdev::dzero(c->d_counters.p, (size_t)FQ_C_STRIPES * FQ_C_STRIDE * 8) || fqdev::sync()) return FQ_ENODEV;
   *out = c.release();
   return FQ_OK;
@@ -524,6 +520,7 @@ static void fold_counters(const uint64_t *striped, uint64_t *cnt) {
   }
 }
 #define CKS(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0)
+static int refuse_length(fq_ctx *c) { c->err = "read length outside [" + std::to_string(FQ_LMIN) + "," + std::to_string(FQ_LMAX) + "]"; return FQ_ELIMIT; }
 
 extern "C" int fq_batch_upload(fq_ctx_t *c, const fq_read_batch_t *in) {
   if (!c || !in || in->n_pairs < 0 || !in->seq || !in->qual || !in->len) return FQ_EINVAL;
@@ -535,7 +532,7 @@ extern "C" int fq_batch_upload(fq_ctx_t *c, const fq_read_batch_t *in) {
   for (size_t i = 0; i < n2; ++i) nb += in->len[i];
   c->n_bases_in = nb;
   for (size_t i = 0; i < n2; ++i)
-    if (in->len[i] < FQ_LMIN || in->len[i] > FQ_LMAX || in->len[i] > in->stride) { c->err = "read length outside [" + std::to_string(FQ_LMIN) + "," + std::to_string(FQ_LMAX) + "]"; return FQ_ELIMIT; }
+    if (in->len[i] < FQ_LMIN || in->len[i] > FQ_LMAX || in->len[i] > in->stride) return refuse_length(c);
   CKM(c->d_seq.ensure((size_t)in->n_pairs * 2 * in->stride + 64));
   CKM(c->d_qual.ensure((size_t)in->n_pairs * 2 * in->stride + 64));
   CKM(c->d_len.ensure((size_t)in->n_pairs * 2 + 1));
@@ -787,6 +784,7 @@ struct Call {
   FqSamArgs emit{};                    // the consumers' view of the call (fq_emit.h), made once per call
   bool emit_ready = false;
   vector<int> sub_max_len, sub_lo;
+  vector<int32_t> sub_whole;           // stage 0, per reference batch: the longest read that trimming leaves whole (known without its quality row; zeros without FilterIn::qual_last)
   // (the arrays of one entry per searched read live in the batch state and keep their pages)
   vector<uint64_t> &aln_off;           // per search index s: its hit list is S.aln[aln_off[s] .. + aln_n[s])
   vector<uint32_t> &aln_n;
@@ -828,80 +826,124 @@ struct Call {
   }
 };
 
-// survivors of stage 0 -> host lists and the reference-batch boundaries among them
-int stage0_lists(Call &K, bool have_len_trim) {
+// ---- stage 0: filter + ordered compaction over every read (GPU), then the reads of surviving pairs as compact ASCII rows ----------------
+// The call may carry several reference batches (READ_BUFFER_SIZE pairs each, src/BwtMapper.h:36): the GPU stages run
+// over all of them at once, the order-dependent host stages walk them one reference batch at a time.
+// The steps are the same for the three kinds of input -- ASCII rows resident in HBM, a packed host batch, FASTQ text resident in HBM -- and each
+// exists once: stage0_filter, stage0_survivors, the survivors' rows (stage0_rows_packed, stage0_rows_text; ASCII rows are resident already),
+// stage0_whole_batch, stage0_finish.  What differs per input is what the filter reads (FilterIn) and where the rows come from.
+struct FilterIn {                      // the filter's view of a packed or text batch: the 24-byte key of every read (head == null: ASCII rows, c->d_seq / d_qual / d_len)
+  const uint64_t *head = nullptr;
+  const uint16_t *len = nullptr;       // every read's length; read when uniform_len <= 0 (a ragged batch)
+  const uint8_t *qual_last = nullptr;  // every read's last quality byte (a packed batch that trims), or null
+  int uniform_len = 0;
+  int body_stride = 0;                 // bytes of a read's packed row, which a ragged read must fit (0: the input has no packed rows)
+  const fq_text_batch *text = nullptr; // a text batch: every read's qualities are resident in HBM (null: a packed batch's are on the host, fq_ctx::pb)
+};
+
+// Filter and compaction, and what the host needs of them: the counts, the longest read of every reference batch, a ragged batch's length counters.
+// Leaves K.dstride: ASCII rows keep theirs, compact rows hold the longest (untrimmed) read of the batch, in 16-byte steps.
+int stage0_filter(Call &K, const FilterIn &in) {
+  fq_ctx *c = K.c;
+  const int n = K.n, n2 = K.n2, n_sub = K.n_sub, B = K.B;
+  const bool ascii = !in.head, se = c->o.single_end != 0, ragged = !ascii && in.uniform_len <= 0;
+  const int n_in = se ? n : n2;                  // rows of the batch's arrays
+  // d_sub_max, per reference batch: the longest read (ASCII rows: trimmed; else untrimmed, ragged batches only), and for a packed or text batch behind it
+  // the longest read that trimming leaves whole and the longest trimmed survivor
+  const size_t n_max = (size_t)(ascii ? 1 : 3) * n_sub;
+  CKM(c->d_filtered.ensure(n2 + 64) && c->d_read_list.ensure(n2) && c->d_sidx.ensure(n2) && c->d_pair_list.ensure(n) && c->d_sub_max.ensure(n_max) && (!ascii || c->d_len_trim.ensure(n2)));
+  CK(fqdev::dzero(c->d_sub_max.p, n_max * 4));
+  // A single-end batch (BwtMapper::SingleEndMapper) holds n reads in n rows; the pair machinery carries each read alone, the rows
+  // of the absent mates (n .. 2n-1) are filtered, empty reads.
+  if (se) CK(fqdev::dfill(c->d_filtered.p + n, 1, (size_t)n));
+  if (se && ascii) CK(fqdev::dzero(c->d_len_trim.p + n, (size_t)n * 4));
+  fqdev::time_begin(FQ_K_PREP);
+  if (ascii) {   // (the filter kernels of all contexts of a device are chained on the device: fqdev::launch_prep)
+    FqPrepArgs a{};
+    a.ix = c->ix->dev; a.o = c->ko; a.seq = c->d_seq.p; a.qual = c->d_qual.p; a.len = c->d_len.p; a.stride = c->stride; a.n_reads = n_in;
+    a.len_trim = c->d_len_trim.p; a.filtered = c->d_filtered.p; a.sub_max = c->d_sub_max.p; a.n_pairs = n; a.batch_pairs = B; a.counters = c->d_counters.p;
+    CK(fqdev::launch_prep(a));
+  } else {
+    FqPrepPackedArgs a{};
+    a.ix = c->ix->dev; a.o = c->ko; a.head = in.head; a.len = ragged ? in.len : nullptr; a.uniform_len = in.uniform_len; a.qual_last = in.qual_last; a.sub_whole = c->d_sub_max.p + n_sub;
+    a.n_reads = n_in; a.filtered = c->d_filtered.p; a.sub_max = c->d_sub_max.p; a.n_pairs = n; a.batch_pairs = B; a.counters = c->d_counters.p;
+    CK(fqdev::launch_prep_packed(a));
+  }
+  CK(fqdev::launch_compact(c->d_filtered.p, n, c->d_read_list.p, c->d_sidx.p, c->d_pair_list.p, c->d_counts.p));
+  fqdev::time_end(FQ_K_PREP);
+  // Only what concerns surviving pairs comes back to the host: in a WGS-like stream that is a fraction of a percent of the batch.
+  int32_t counts[2] = {0, 0};
+  c->h_sub_max.assign(n_sub, in.uniform_len);   // longest read per reference batch
+  K.sub_whole.assign(n_sub, 0);
+  std::vector<uint64_t> striped(ragged ? (size_t)FQ_C_STRIPES * FQ_C_STRIDE : 0);   // FQ_C_BASES, FQ_C_BADLEN
+  CKS(d2h_staged(c, counts, c->d_counts.p, 8));
+  if (in.qual_last) CKS(d2h_staged(c, K.sub_whole.data(), c->d_sub_max.p + n_sub, (size_t)n_sub * 4));
+  if (ascii || ragged) CKS(d2h_staged(c, c->h_sub_max.data(), c->d_sub_max.p, (size_t)n_sub * 4));
+  if (ragged) CKS(d2h_staged(c, striped.data(), c->d_counters.p, striped.size() * 8));
+  CKS(sync_staged(c));
+  K.trace("  stage0: filter + compaction on the device");
+  if (ragged) {
+    uint64_t folded[FQ_C_COUNT];
+    fold_counters(striped.data(), folded);
+    if (folded[FQ_C_BADLEN]) return refuse_length(c);
+    // A ragged row longer than its packed row would be unpacked from its neighbour's bytes.  (Packed batches only: the rows of a text batch are gathered by
+    // the offsets of their records, ASCII rows are held to their stride by fq_batch_upload, a uniform length to body_stride by fq_align_packed.)
+    for (int sb = 0; in.body_stride && sb < n_sub; ++sb)
+      if (((int64_t)c->h_sub_max[sb] + 3) / 4 > (int64_t)in.body_stride) { c->err = "a read is longer than body_stride holds"; return FQ_EINVAL; }
+    c->n_bases_in = (int64_t)folded[FQ_C_BASES];
+  } else if (!ascii) c->n_bases_in = (int64_t)n_in * in.uniform_len;   // (ASCII rows: counted and checked by fq_batch_upload)
+  K.n_search = counts[0]; K.n_surv = counts[1];
+  K.dstride = ascii ? c->stride : (std::max(1, *std::max_element(c->h_sub_max.begin(), c->h_sub_max.end())) + 15) & ~15;
+  return FQ_OK;
+}
+
+// debug: the per-read arrays of the whole batch for the stage dump, valid after the next wait (d_len_all: every read's trimmed length, or null)
+int stage0_debug_fetch(fq_ctx *c, int n2, const int32_t *d_len_all) {
+  c->h_filtered.clear(); c->h_len_trim.clear();
+  if (!c->debug) return FQ_OK;
+  c->h_filtered.resize(n2);
+  CKS(d2h_staged(c, c->h_filtered.data(), c->d_filtered.p, n2));
+  if (d_len_all) { c->h_len_trim.resize(n2); CKS(d2h_staged(c, c->h_len_trim.data(), d_len_all, (size_t)n2 * 4)); }
+  return FQ_OK;
+}
+// The survivors on the device -- per-read info by survivor row (d_surv) -- and the host's lists of them with the reference-batch boundaries.
+// ASCII rows stay where they lie (search index -> row of the batch, as the compaction left it).  Of a packed or text batch only the survivors' rows
+// are made (compact): d_read_list is rewritten as search index -> compact row, d_row_map is compact row -> row of the batch, and crow (packed bulk
+// upload, else null) the reverse.
+int stage0_survivors(Call &K, bool compact, int32_t *crow) {
   fq_ctx *c = K.c;
   const int n_surv = K.n_surv;
-  CKM(c->p_pairs.ensure((size_t)n_surv + 1) && c->p_surv.ensure((size_t)n_surv * 2 + 1));
+  const size_t nrow = (size_t)n_surv * 2;
+  CKM(c->d_surv.ensure(nrow + 1));
+  if (compact) {
+    CKM(c->d_row_map.ensure(nrow + 1) && c->d_len_c.ensure(nrow + 1) && c->d_len_trim.ensure(nrow + 1));
+    CK(fqdev::launch_surv_map(c->d_pair_list.p, n_surv, K.n, c->d_filtered.p, c->d_sidx.p, c->d_surv.p, c->d_row_map.p, c->d_read_list.p, crow));
+  } else CK(fqdev::launch_surv_gather(c->d_pair_list.p, n_surv, K.n, c->d_len_trim.p, c->d_filtered.p, c->d_sidx.p, c->d_surv.p));
+  if (!compact) CKS(stage0_debug_fetch(c, K.n2, c->d_len_trim.p));   // (ASCII rows: the filter trimmed every read; the arrays come with the lists' wait)
+  CKM(c->p_pairs.ensure((size_t)n_surv + 1) && c->p_surv.ensure(nrow + 1));
   CK(fqdev::copy_pinned(c->p_pairs.p, c->d_pair_list.p, (size_t)n_surv * 4, 0));
-  CK(fqdev::copy_pinned(c->p_surv.p, c->d_surv.p, (size_t)n_surv * 2 * sizeof(FqSurvInfo), 0));
+  CK(fqdev::copy_pinned(c->p_surv.p, c->d_surv.p, nrow * sizeof(FqSurvInfo), 0));
   CKS(sync_staged(c));
   c->stats.d2h_bytes += (size_t)n_surv * (4 + 2 * sizeof(FqSurvInfo));
   c->h_pair_list = c->p_pairs.p; c->h_surv = c->p_surv.p;   // read where they land
-  (void)have_len_trim;
   K.sub_lo.assign(K.n_sub + 1, 0);
   for (int sb = 0; sb <= K.n_sub; ++sb)   // (the list is ascending)
     K.sub_lo[sb] = (int)(std::lower_bound(c->h_pair_list, c->h_pair_list + n_surv, (int32_t)std::min<int64_t>((int64_t)sb * K.B, INT32_MAX)) - c->h_pair_list);
   K.sub_lo[K.n_sub] = n_surv;
+  K.trace("  stage0: survivors' lists D2H");
   return FQ_OK;
 }
-void stage0_sub_max(Call &K) {
-  K.max_len_all = 1;
-  K.sub_max_len.assign(K.n_sub, 1);
-  for (int sb = 0; sb < K.n_sub; ++sb) {
-    K.sub_max_len[sb] = std::max(1, K.c->h_sub_max[sb]);
-    K.max_len_all = std::max(K.max_len_all, K.sub_max_len[sb]);
-  }
-}
 
-// ---- stage 0, ASCII rows resident in HBM: encode + trim + filter + ordered compaction (GPU) ---------------------------
-// The call may carry several reference batches (READ_BUFFER_SIZE pairs each, src/BwtMapper.h:36): the GPU stages run
-// over all of them at once, the order-dependent host stages walk them one reference batch at a time.
-int stage0_ascii(Call &K) {
+// bwa_trim_read over the compact rows: trimmed lengths, and the longest trimmed survivor of every reference batch
+FqTrimArgs stage0_trim_args(const Call &K, const uint8_t *qual, int qual_stride, const int32_t *row_map) {
   fq_ctx *c = K.c;
-  const fq_index *ix = c->ix;
-  const int n = K.n, n2 = K.n2, n_sub = K.n_sub, B = K.B;
-  CKM(c->d_len_trim.ensure(n2) && c->d_filtered.ensure(n2 + 64) && c->d_read_list.ensure(n2) &&
-      c->d_sidx.ensure(n2) && c->d_pair_list.ensure(n) && c->d_sub_max.ensure(n_sub));
-  CK(fqdev::dzero(c->d_sub_max.p, (size_t)n_sub * 4));
-  // (the filter kernels of all contexts of a device are chained on the device: fqdev::launch_prep)
-  FqPrepArgs a{};
-  a.ix = ix->dev; a.o = c->ko; a.seq = c->d_seq.p; a.qual = c->d_qual.p; a.len = c->d_len.p; a.stride = c->stride; a.n_reads = c->o.single_end ? n : n2;
-  if (c->o.single_end) {   // the rows of the absent mates: filtered, so that the pair machinery carries each read alone
-    CK(fqdev::dfill(c->d_filtered.p + n, 1, (size_t)n));
-    CK(fqdev::dzero(c->d_len_trim.p + n, (size_t)n * 4));
-  }
-  a.len_trim = c->d_len_trim.p; a.filtered = c->d_filtered.p; a.sub_max = c->d_sub_max.p; a.n_pairs = n; a.batch_pairs = B;
-  a.counters = c->d_counters.p;
-  fqdev::time_begin(FQ_K_PREP);
-  CK(fqdev::launch_prep(a));
-  CK(fqdev::launch_compact(c->d_filtered.p, n, c->d_read_list.p, c->d_sidx.p, c->d_pair_list.p, c->d_counts.p));
-  fqdev::time_end(FQ_K_PREP);
-  // Only what concerns surviving pairs comes back to the host: in a WGS-like stream that is a fraction of a percent of the
-  // batch.  (Debug mode also fetches the per-read arrays of the whole batch for the stage dump.)
-  int32_t counts[2] = {0, 0};
-  c->h_sub_max.resize(n_sub);
-  CKS(d2h_staged(c, counts, c->d_counts.p, 8));
-  CKS(d2h_staged(c, c->h_sub_max.data(), c->d_sub_max.p, (size_t)n_sub * 4));
-  CKS(sync_staged(c));
-  K.trace("  stage0: filter + compaction on the device");
-  K.n_search = counts[0]; K.n_surv = counts[1];
-  CKM(c->d_surv.ensure((size_t)K.n_surv * 2 + 1));
-  CK(fqdev::launch_surv_gather(c->d_pair_list.p, K.n_surv, n, c->d_len_trim.p, c->d_filtered.p, c->d_sidx.p, c->d_surv.p));
-  if (c->debug) {
-    c->h_filtered.resize(n2);
-    c->h_len_trim.resize(n2);
-    CKS(d2h_staged(c, c->h_filtered.data(), c->d_filtered.p, n2));
-    CKS(d2h_staged(c, c->h_len_trim.data(), c->d_len_trim.p, (size_t)n2 * 4));
-  } else { c->h_filtered.clear(); c->h_len_trim.clear(); }
-  int rc = stage0_lists(K, true);
-  if (rc) return rc;
-  stage0_sub_max(K);
-  K.dseq = c->d_seq.p; K.dstride = c->stride; K.dlen_trim = c->d_len_trim.p; K.dread_list = c->d_read_list.p;
-  return FQ_OK;
+  FqTrimArgs ta{};
+  ta.o = c->ko; ta.qual = qual; ta.qual_stride = qual_stride; ta.row_map = row_map; ta.len = c->d_len_c.p; ta.n_rows = 2 * K.n_surv; ta.len_trim = c->d_len_trim.p;
+  ta.pair_list = c->d_pair_list.p; ta.batch_pairs = K.B; ta.sub_max = c->d_sub_max.p + 2 * K.n_sub;
+  return ta;
 }
 
-// ---- stage 0, packed host batch (SURVEY 8d boundary) ---------------------------------------------------------------------
+// ---- the survivors' rows of a packed host batch (SURVEY 8d boundary) -------------------------------------------------------------------
 // Only the 24-byte filter key of every read crosses PCIe (its upload may have been started by fq_packed_prefetch and then
 // ran under the previous call's kernels); the full rows -- and, when --q trimming is on, the qualities -- follow for the
 // reads of surviving pairs only, and are unpacked into the compact ASCII rows the later kernels read.
@@ -923,83 +965,26 @@ int head_upload(fq_ctx *c, const fq_packed_batch_t *b, int slot) {
   CK(fqdev::copy_record(slot));
   return FQ_OK;
 }
-int stage0_packed(Call &K) {
+// body rows (+ exceptions, + qualities when trimming) -> compact ASCII rows.  bulk: the whole body goes up and the device gathers (many survivors);
+// else the host gathers the survivors' rows into pinned staging (a few thousand rows per reference batch in a WGS stream).
+int stage0_rows_packed(Call &K, bool bulk) {
   fq_ctx *c = K.c;
-  const fq_index *ix = c->ix;
   const fq_packed_batch_t &pb = c->pb;
-  const int n = K.n, n2 = K.n2, n_sub = K.n_sub, B = K.B;
-  // A single-end batch (BwtMapper::SingleEndMapper) holds n reads in n rows; the pair machinery carries each read alone, the rows
-  // of the absent mates (n .. 2n-1) are filtered, empty reads, as in the ASCII path.
-  const bool se = c->o.single_end != 0;
-  const int n_in = se ? n : n2;                  // rows of the batch's arrays
-  const bool ragged = pb.uniform_len <= 0;
-  const bool trim = c->o.trim_qual >= 1;
-  const int slot = c->head_slot;   // chosen by fq_align_packed: the buffer the batch was prefetched into, else a free one (uploaded now)
-  CK(fqdev::compute_wait_copy(slot));
-  const bool have_qlast = trim && pb.qual_last != nullptr;
-  CKM(c->d_filtered.ensure(n2 + 64) && c->d_read_list.ensure(n2) && c->d_sidx.ensure(n2) && c->d_pair_list.ensure(n) && c->d_sub_max.ensure((size_t)3 * n_sub));
-  CK(fqdev::dzero(c->d_sub_max.p, (size_t)3 * n_sub * 4));
-  if (se) CK(fqdev::dfill(c->d_filtered.p + n, 1, (size_t)n));
-  FqPrepPackedArgs a{};
-  a.qual_last = have_qlast ? c->d_qlast[slot].p : nullptr; a.sub_whole = c->d_sub_max.p + n_sub;
-  a.ix = ix->dev; a.o = c->ko; a.head = c->d_head[slot].p; a.len = ragged ? c->d_hlen[slot].p : nullptr; a.uniform_len = pb.uniform_len;
-  a.n_reads = n_in; a.filtered = c->d_filtered.p; a.sub_max = c->d_sub_max.p; a.n_pairs = n; a.batch_pairs = B; a.counters = c->d_counters.p;
-  fqdev::time_begin(FQ_K_PREP);
-  CK(fqdev::launch_prep_packed(a));
-  CK(fqdev::launch_compact(c->d_filtered.p, n, c->d_read_list.p, c->d_sidx.p, c->d_pair_list.p, c->d_counts.p));
-  fqdev::time_end(FQ_K_PREP);
-  int32_t counts[2] = {0, 0};
-  uint64_t lcnt[2] = {0, 0};   // FQ_C_BASES, FQ_C_BADLEN (ragged batches)
-  c->h_sub_max.assign(n_sub, pb.uniform_len);   // longest untrimmed read per reference batch
-  vector<int32_t> sub_whole(n_sub, 0);          // longest read trimming leaves whole (known without its quality row)
-  CKS(d2h_staged(c, counts, c->d_counts.p, 8));
-  if (have_qlast) CKS(d2h_staged(c, sub_whole.data(), c->d_sub_max.p + n_sub, (size_t)n_sub * 4));
-  std::vector<uint64_t> striped(ragged ? (size_t)FQ_C_STRIPES * FQ_C_STRIDE : 0);
-  if (ragged) {
-    CKS(d2h_staged(c, c->h_sub_max.data(), c->d_sub_max.p, (size_t)n_sub * 4));
-    CKS(d2h_staged(c, striped.data(), c->d_counters.p, striped.size() * 8));
-  }
-  CKS(sync_staged(c));
-  if (ragged) {
-    uint64_t folded[FQ_C_COUNT];
-    fold_counters(striped.data(), folded);
-    lcnt[0] = folded[FQ_C_BASES]; lcnt[1] = folded[FQ_C_BADLEN];
-    if (lcnt[1]) { c->err = "read length outside [" + std::to_string(FQ_LMIN) + "," + std::to_string(FQ_LMAX) + "]"; return FQ_ELIMIT; }
-    for (int sb = 0; sb < n_sub; ++sb)   // a ragged row longer than its packed row would be unpacked from its neighbour's bytes
-      if (((int64_t)c->h_sub_max[sb] + 3) / 4 > (int64_t)pb.body_stride) { c->err = "a read is longer than body_stride holds"; return FQ_EINVAL; }
-    c->n_bases_in = (int64_t)lcnt[0];
-  } else c->n_bases_in = (int64_t)n_in * pb.uniform_len;
-  const int n_search = counts[0], n_surv = counts[1], nrow = 2 * n_surv;
-  K.n_search = n_search; K.n_surv = n_surv;
-  const int64_t bulk_min = c->kn.packed_bulk_min >= 0 ? c->kn.packed_bulk_min : (int64_t)n / 8;
-  const bool bulk = !se && n_surv > 0 && (int64_t)n_surv >= bulk_min;   // many survivors: upload the whole body, gather on the device (single-end batches: rows gathered on the host, the absent mates' among them as empty rows)
-  CKM(c->d_surv.ensure((size_t)nrow + 1) && c->d_row_map.ensure((size_t)nrow + 1) && c->d_len_c.ensure((size_t)nrow + 1) && c->d_len_trim.ensure((size_t)nrow + 1));
-  const bool need_crow = bulk && pb.n_exc > 0;   // batch row -> compact row (-1: not unpacked), for the exception list of the whole batch
-  if (need_crow) { CKM(c->d_crow.ensure(n2)); CK(fqdev::dfill(c->d_crow.p, 0xff, (size_t)n2 * 4)); }
-  // d_read_list is rewritten as search index -> compact row
-  CK(fqdev::launch_surv_map(c->d_pair_list.p, n_surv, n, c->d_filtered.p, c->d_sidx.p, c->d_surv.p, c->d_row_map.p, c->d_read_list.p, need_crow ? c->d_crow.p : nullptr));
-  int rc = stage0_lists(K, false);
-  if (rc) return rc;
-  // ---- the reads of surviving pairs: body rows (+ exceptions, + qualities when trimming) -> compact ASCII rows ----
-  const int body_stride = pb.body_stride;
-  int max_full = 1;
-  for (int sb = 0; sb < n_sub; ++sb) max_full = std::max(max_full, c->h_sub_max[sb]);
-  const int cstride = (max_full + 15) & ~15;
+  const int n = K.n, n2 = K.n2, nrow = 2 * K.n_surv, body_stride = pb.body_stride, cstride = K.dstride;
+  const bool se = c->o.single_end != 0, ragged = pb.uniform_len <= 0, trim = c->o.trim_qual >= 1;
   CKM(c->d_seq.ensure((size_t)nrow * cstride + 64));
   FqUnpackArgs ua{};
   ua.body_stride = body_stride; ua.uniform_len = pb.uniform_len; ua.n_rows = nrow; ua.seq = c->d_seq.p; ua.stride = cstride;
   ua.len_out = c->d_len_c.p; ua.len_trim = c->d_len_trim.p;
   FqPatchArgs pa{};
   pa.seq = c->d_seq.p; pa.stride = cstride;
-  FqTrimArgs ta{};
-  ta.o = c->ko; ta.qual_stride = pb.qual_stride; ta.len = c->d_len_c.p; ta.n_rows = nrow; ta.len_trim = c->d_len_trim.p;
-  ta.pair_list = c->d_pair_list.p; ta.batch_pairs = B; ta.sub_max = c->d_sub_max.p + 2 * n_sub;
+  FqTrimArgs ta = stage0_trim_args(K, nullptr, pb.qual_stride, nullptr);
   if (nrow && bulk) {
     CKM(c->d_body.ensure((size_t)n2 * body_stride + 64));
     CK(fqdev::h2d(c->d_body.p, pb.body, (size_t)n2 * body_stride));
     c->stats.h2d_bytes += (size_t)n2 * body_stride;
     ua.body = c->d_body.p; ua.row_map = c->d_row_map.p;
-    if (ragged) ua.len = c->d_hlen[slot].p;
+    if (ragged) ua.len = c->d_hlen[c->head_slot].p;
     if (pb.n_exc) {
       CKM(c->d_exc.ensure((size_t)pb.n_exc + 1));
       CK(fqdev::h2d(c->d_exc.p, pb.exc, (size_t)pb.n_exc * 8));
@@ -1013,7 +998,6 @@ int stage0_packed(Call &K) {
       ta.qual = c->d_pqual.p; ta.row_map = c->d_row_map.p;
     }
   } else if (nrow) {
-    // few survivors: gather their rows into pinned staging on the host (a few thousand rows per reference batch in a WGS stream)
     CKM(c->p_body.ensure((size_t)nrow * body_stride + 64) && c->d_body.ensure((size_t)nrow * body_stride + 64));
     const bool row_lens = ragged || se;   // per-row lengths travel with the rows (single-end: the absent mates' rows have none)
     if (row_lens) CKM(c->p_hlen.ensure((size_t)nrow + 8) && c->d_blen.ensure((size_t)nrow + 8));
@@ -1066,99 +1050,18 @@ int stage0_packed(Call &K) {
     if (trim) CK(fqdev::launch_trim(ta));
   }
   fqdev::time_end(FQ_K_PREP);
-  // the longest trimmed read among the survivors of every reference batch (the records themselves are set up on the device)
-  vector<int32_t> surv_max(n_sub, 0);
-  if (nrow && trim) { CKS(d2h_staged(c, surv_max.data(), c->d_sub_max.p + 2 * n_sub, (size_t)n_sub * 4)); CKS(sync_staged(c)); c->stats.d2h_bytes += (size_t)n_sub * 4; }
-  // infer_isize's max_len is the longest trimmed read of the whole reference batch, filtered reads included (bwape.c:60-61).
-  // Without trimming that is the longest read (known above).  With trimming, the trimmed lengths of the survivors are known, and
-  // so is the length of every read that trimming leaves whole (from its last quality byte, fq_prep_packed_thread); every other
-  // read is shorter than the batch's longest.  When those known lengths reach the batch's longest read they are the maximum;
-  // otherwise -- and for the debug dump, which lists every read -- the qualities of all reads go to the device.
-  for (int sb = 0; sb < n_sub; ++sb) surv_max[sb] = std::max(surv_max[sb], (int)sub_whole[sb]);
-  bool need_all = trim && c->debug;
-  if (trim) for (int sb = 0; sb < n_sub; ++sb) if (surv_max[sb] < c->h_sub_max[sb]) need_all = true;
-  c->h_filtered.clear(); c->h_len_trim.clear();
-  if (need_all) {
-    CKM(c->d_pqual.ensure((size_t)n_in * pb.qual_stride + 64) && c->d_len_all.ensure(n2));
-    CK(fqdev::h2d(c->d_pqual.p, pb.qual, (size_t)n_in * pb.qual_stride));
-    c->stats.h2d_bytes += (size_t)n_in * pb.qual_stride;
-    CK(fqdev::dzero(c->d_sub_max.p, (size_t)n_sub * 4));
-    if (se) CK(fqdev::dzero(c->d_len_all.p + n, (size_t)n * 4));
-    FqTrimAllArgs aa{};
-    aa.o = c->ko; aa.qual = c->d_pqual.p; aa.qual_stride = pb.qual_stride; aa.len = ragged ? c->d_hlen[slot].p : nullptr; aa.uniform_len = pb.uniform_len;
-    aa.n_reads = n_in; aa.n_pairs = n; aa.batch_pairs = B; aa.len_trim = c->d_len_all.p; aa.sub_max = c->d_sub_max.p;
-    CK(fqdev::launch_trim_all(aa));
-    CKS(d2h_staged(c, c->h_sub_max.data(), c->d_sub_max.p, (size_t)n_sub * 4));
-    if (c->debug) { c->h_len_trim.resize(n2); CKS(d2h_staged(c, c->h_len_trim.data(), c->d_len_all.p, (size_t)n2 * 4)); }
-    CKS(sync_staged(c));
-  } else if (trim) {
-    for (int sb = 0; sb < n_sub; ++sb) c->h_sub_max[sb] = surv_max[sb];
-  }
-  if (c->debug) {
-    c->h_filtered.resize(n2);
-    CKS(d2h_staged(c, c->h_filtered.data(), c->d_filtered.p, n2));
-    CKS(sync_staged(c));
-    if (c->h_len_trim.empty()) { c->h_len_trim.resize(n2); for (int r = 0; r < n2; ++r) c->h_len_trim[r] = r >= n_in ? 0 : ragged ? (int)pb.len[r] : pb.uniform_len; }
-  }
-  stage0_sub_max(K);
-  K.dseq = c->d_seq.p; K.dstride = cstride; K.dlen_trim = c->d_len_trim.p; K.dread_list = c->d_read_list.p;
   return FQ_OK;
 }
 
-// ---- stage 0, FASTQ text resident in HBM (the device front end's batches, fq_frontend.cpp) --------------------------------------------
+// ---- the survivors' rows of FASTQ text resident in HBM (the device front end's batches, fq_frontend.cpp) --------------------------------
 // The filter's keys are in place (fqt_piece_thread / fqt_slot_bases_thread wrote what fq_pack_reads_into writes on the host), so the filter
 // and the compaction run as for a packed batch without an upload; the reads of surviving pairs are gathered from the text into the
 // compact rows every later kernel reads, and come to the host for the consumers (bases, qualities, names of the survivors only).
-int stage0_text(Call &K) {
+// (The copies to the host are in flight when this returns: stage0_whole_batch waits for them.)
+int stage0_rows_text(Call &K) {
   fq_ctx *c = K.c;
-  const fq_index *ix = c->ix;
   const fq_text_batch &tb = *c->tb;
-  const int n = K.n, n2 = K.n2, n_sub = K.n_sub, B = K.B;
-  const bool se = c->o.single_end != 0;
-  const int n_in = se ? n : n2;
-  const bool ragged = tb.uniform_len <= 0;
-  const bool trim = c->o.trim_qual >= 1;
-  CKM(c->d_filtered.ensure(n2 + 64) && c->d_read_list.ensure(n2) && c->d_sidx.ensure(n2) && c->d_pair_list.ensure(n) && c->d_sub_max.ensure((size_t)3 * n_sub));
-  CK(fqdev::dzero(c->d_sub_max.p, (size_t)3 * n_sub * 4));
-  if (se) CK(fqdev::dfill(c->d_filtered.p + n, 1, (size_t)n));
-  FqPrepPackedArgs a{};
-  a.qual_last = nullptr; a.sub_whole = nullptr;
-  a.ix = ix->dev; a.o = c->ko; a.head = tb.d_head; a.len = ragged ? tb.d_hlen : nullptr; a.uniform_len = tb.uniform_len;
-  a.n_reads = n_in; a.filtered = c->d_filtered.p; a.sub_max = c->d_sub_max.p; a.n_pairs = n; a.batch_pairs = B; a.counters = c->d_counters.p;
-  fqdev::time_begin(FQ_K_PREP);
-  CK(fqdev::launch_prep_packed(a));
-  CK(fqdev::launch_compact(c->d_filtered.p, n, c->d_read_list.p, c->d_sidx.p, c->d_pair_list.p, c->d_counts.p));
-  fqdev::time_end(FQ_K_PREP);
-  int32_t counts[2] = {0, 0};
-  uint64_t lcnt[2] = {0, 0};
-  c->h_sub_max.assign(n_sub, tb.uniform_len);
-  CKS(d2h_staged(c, counts, c->d_counts.p, 8));
-  std::vector<uint64_t> striped(ragged ? (size_t)FQ_C_STRIPES * FQ_C_STRIDE : 0);
-  if (ragged) {
-    CKS(d2h_staged(c, c->h_sub_max.data(), c->d_sub_max.p, (size_t)n_sub * 4));
-    CKS(d2h_staged(c, striped.data(), c->d_counters.p, striped.size() * 8));
-  }
-  CKS(sync_staged(c));
-  K.trace("  stage0: filter + compaction of the text batch");
-  if (ragged) {
-    uint64_t folded[FQ_C_COUNT];
-    fold_counters(striped.data(), folded);
-    lcnt[0] = folded[FQ_C_BASES]; lcnt[1] = folded[FQ_C_BADLEN];
-    if (lcnt[1]) { c->err = "read length outside [" + std::to_string(FQ_LMIN) + "," + std::to_string(FQ_LMAX) + "]"; return FQ_ELIMIT; }
-    c->n_bases_in = (int64_t)lcnt[0];
-  } else c->n_bases_in = (int64_t)n_in * tb.uniform_len;
-  const int n_search = counts[0], n_surv = counts[1], nrow = 2 * n_surv;
-  K.n_search = n_search; K.n_surv = n_surv;
-  CKM(c->d_surv.ensure((size_t)nrow + 1) && c->d_row_map.ensure((size_t)nrow + 1) && c->d_len_c.ensure((size_t)nrow + 1) && c->d_len_trim.ensure((size_t)nrow + 1));
-  CK(fqdev::launch_surv_map(c->d_pair_list.p, n_surv, n, c->d_filtered.p, c->d_sidx.p, c->d_surv.p, c->d_row_map.p, c->d_read_list.p, nullptr));
-  int rc = stage0_lists(K, false);
-  if (rc) return rc;
-  K.trace("  stage0: survivors' lists D2H");
-  // ---- the reads of surviving pairs: rows, qualities and names out of the text ----
-  int max_full = 1;
-  for (int sb = 0; sb < n_sub; ++sb) max_full = std::max(max_full, c->h_sub_max[sb]);
-  const int cstride = (max_full + 15) & ~15;
-  const int ns = tb.name_stride;
+  const int nrow = 2 * K.n_surv, ns = tb.name_stride, cstride = K.dstride;
   c->c_stride = cstride; c->c_name_stride = ns;
   CKM(c->d_seq.ensure((size_t)nrow * cstride + 64) && c->d_pqual.ensure((size_t)nrow * cstride + 64) && c->d_cnames.ensure((size_t)nrow * ns + 64));
   // (the consumers on the device read the rows where they lie: FQ_EMIT_DEVICE_ONLY leaves them there)
@@ -1168,16 +1071,11 @@ int stage0_text(Call &K) {
   fqdev::time_begin(FQ_K_PREP);
   if (nrow) {
     FqTextGatherArgs g{};
-    g.text[0] = tb.d_text[0]; g.text[1] = tb.d_text[1]; g.rec = tb.d_rec; g.names = tb.d_names; g.name_stride = ns; g.n_pairs = n; g.single_end = se ? 1 : 0;
+    g.text[0] = tb.d_text[0]; g.text[1] = tb.d_text[1]; g.rec = tb.d_rec; g.names = tb.d_names; g.name_stride = ns; g.n_pairs = K.n; g.single_end = c->o.single_end ? 1 : 0;
     g.pair_list = c->d_pair_list.p; g.n_out = nrow; g.seq = c->d_seq.p; g.qual = c->d_pqual.p; g.stride = cstride;
     g.len_out = c->d_len_c.p; g.len_trim = c->d_len_trim.p; g.names_out = c->d_cnames.p;
     CK(fqdev::launch_text_gather(g));
-    if (trim) {
-      FqTrimArgs ta{};
-      ta.o = c->ko; ta.qual = c->d_pqual.p; ta.qual_stride = cstride; ta.row_map = nullptr; ta.len = c->d_len_c.p; ta.n_rows = nrow; ta.len_trim = c->d_len_trim.p;
-      ta.pair_list = c->d_pair_list.p; ta.batch_pairs = B; ta.sub_max = c->d_sub_max.p + 2 * n_sub;
-      CK(fqdev::launch_trim(ta));
-    }
+    if (c->o.trim_qual >= 1) CK(fqdev::launch_trim(stage0_trim_args(K, c->d_pqual.p, cstride, nullptr)));
     if (host_rows) {
       CK(fqdev::copy_pinned(c->p_cseq.p, c->d_seq.p, (size_t)nrow * cstride, 0));
       CK(fqdev::copy_pinned(c->p_cqual.p, c->d_pqual.p, (size_t)nrow * cstride, 0));
@@ -1187,40 +1085,248 @@ int stage0_text(Call &K) {
     }
   }
   fqdev::time_end(FQ_K_PREP);
-  // infer_isize's max_len is the longest trimmed read of the whole reference batch, filtered reads included (libbwa/bwape.c:60-61): every
-  // read's qualities are in HBM, so bwa_trim_read runs over all of them where they lie
-  c->h_filtered.clear(); c->h_len_trim.clear(); c->h_len_all.clear();
-  if (trim) {
+  return FQ_OK;
+}
+
+// The longest trimmed read of every reference batch (h_sub_max) of a packed or text batch, and the debug arrays.
+// infer_isize's max_len is the longest trimmed read of the whole reference batch, filtered reads included (libbwa/bwape.c:60-61).
+// Without trimming that is the longest read (known since the filter).  A text batch has every read's qualities in HBM, so bwa_trim_read
+// runs over all of them where they lie.  Of a packed batch the trimmed lengths of the survivors are known, and so is the length of every
+// read that trimming leaves whole (sub_whole: from its last quality byte, fq_prep_packed_thread); every other read is shorter than the
+// batch's longest.  When those known lengths reach the batch's longest read they are the maximum; otherwise -- and for the debug dump,
+// which lists every read -- the qualities of all reads go to the device.
+int stage0_whole_batch(Call &K, const FilterIn &in) {
+  fq_ctx *c = K.c;
+  const fq_text_batch *tb = in.text;
+  const int n = K.n, n2 = K.n2, n_sub = K.n_sub, nrow = 2 * K.n_surv;
+  const bool se = c->o.single_end != 0, ragged = in.uniform_len <= 0, trim = c->o.trim_qual >= 1;
+  const int n_in = se ? n : n2;
+  bool need_all = trim && (tb || c->debug);
+  if (trim && !tb) {
+    vector<int32_t> surv_max(n_sub, 0);       // the longest trimmed read among the survivors of every reference batch
+    if (nrow) {
+      CKS(d2h_staged(c, surv_max.data(), c->d_sub_max.p + 2 * n_sub, (size_t)n_sub * 4));
+      CKS(sync_staged(c));
+      c->stats.d2h_bytes += (size_t)n_sub * 4;   // (the one fetch of d_sub_max that is counted; a text batch never makes it)
+    }
+    for (int sb = 0; sb < n_sub; ++sb) {
+      surv_max[sb] = std::max(surv_max[sb], K.sub_whole[sb]);
+      if (surv_max[sb] < c->h_sub_max[sb]) need_all = true;
+    }
+    if (!need_all) c->h_sub_max = surv_max;
+  }
+  if (need_all) {
     CKM(c->d_len_all.ensure(n2));
+    if (!tb) {
+      CKM(c->d_pqual.ensure((size_t)n_in * c->pb.qual_stride + 64));
+      CK(fqdev::h2d(c->d_pqual.p, c->pb.qual, (size_t)n_in * c->pb.qual_stride));
+      c->stats.h2d_bytes += (size_t)n_in * c->pb.qual_stride;
+    }
     CK(fqdev::dzero(c->d_sub_max.p, (size_t)n_sub * 4));
     if (se) CK(fqdev::dzero(c->d_len_all.p + n, (size_t)n * 4));
-    FqTextTrimArgs aa{};
-    aa.o = c->ko; aa.text[0] = tb.d_text[0]; aa.text[1] = tb.d_text[1]; aa.rec = tb.d_rec; aa.n_rows = n_in; aa.n_pairs = n; aa.batch_pairs = B;
-    aa.len_trim = c->d_len_all.p; aa.sub_max = c->d_sub_max.p;
-    CK(fqdev::launch_text_trim_all(aa));
+    if (tb) {
+      FqTextTrimArgs aa{};
+      aa.o = c->ko; aa.text[0] = tb->d_text[0]; aa.text[1] = tb->d_text[1]; aa.rec = tb->d_rec; aa.n_rows = n_in; aa.n_pairs = n; aa.batch_pairs = K.B;
+      aa.len_trim = c->d_len_all.p; aa.sub_max = c->d_sub_max.p;
+      CK(fqdev::launch_text_trim_all(aa));
+    } else {
+      FqTrimAllArgs aa{};
+      aa.o = c->ko; aa.qual = c->d_pqual.p; aa.qual_stride = c->pb.qual_stride; aa.len = ragged ? in.len : nullptr; aa.uniform_len = in.uniform_len;
+      aa.n_reads = n_in; aa.n_pairs = n; aa.batch_pairs = K.B; aa.len_trim = c->d_len_all.p; aa.sub_max = c->d_sub_max.p;
+      CK(fqdev::launch_trim_all(aa));
+    }
     CKS(d2h_staged(c, c->h_sub_max.data(), c->d_sub_max.p, (size_t)n_sub * 4));
-    if (c->debug) { c->h_len_trim.resize(n2); CKS(d2h_staged(c, c->h_len_trim.data(), c->d_len_all.p, (size_t)n2 * 4)); }
   }
-  if (c->debug) {
-    c->h_filtered.resize(n2);
-    CKS(d2h_staged(c, c->h_filtered.data(), c->d_filtered.p, n2));
-    c->h_len_all.assign(n2, 0);
-    CKS(d2h_staged(c, c->h_len_all.data(), tb.d_hlen, (size_t)n_in * 2));
+  CKS(stage0_debug_fetch(c, n2, need_all ? c->d_len_all.p : nullptr));
+  if (tb) c->h_len_all.clear();   // every row's length, for the dump of a text batch
+  if (tb && c->debug) { c->h_len_all.assign(n2, 0); CKS(d2h_staged(c, c->h_len_all.data(), tb->d_hlen, (size_t)n_in * 2)); }
+  // one wait for what was asked for above -- and for the rows of a text batch on their way to the host, whatever else there is
+  if (need_all || c->debug || tb) CKS(sync_staged(c));
+  if (c->debug && c->h_len_trim.empty()) {   // no trimming ran: the lengths as they are
+    c->h_len_trim.resize(n2);
+    for (int r = 0; r < n2; ++r) c->h_len_trim[r] = r >= n_in ? 0 : tb ? (int)c->h_len_all[r] : ragged ? (int)c->pb.len[r] : in.uniform_len;
   }
-  CKS(sync_staged(c));
-  if (c->debug && c->h_len_trim.empty()) { c->h_len_trim.resize(n2); for (int r = 0; r < n2; ++r) c->h_len_trim[r] = r >= n_in ? 0 : (int)c->h_len_all[r]; }
-  stage0_sub_max(K);
+  return FQ_OK;
+}
+
+// where the kernels after the filter find the reads, and the longest read of every reference batch as the later stages want it
+void stage0_finish(Call &K) {
+  fq_ctx *c = K.c;
+  K.max_len_all = 1;
+  K.sub_max_len.assign(K.n_sub, 1);
+  for (int sb = 0; sb < K.n_sub; ++sb) {
+    K.sub_max_len[sb] = std::max(1, c->h_sub_max[sb]);
+    K.max_len_all = std::max(K.max_len_all, K.sub_max_len[sb]);
+  }
+  K.dseq = c->d_seq.p; K.dlen_trim = c->d_len_trim.p; K.dread_list = c->d_read_list.p;
+}
+
+int stage0_ascii(Call &K) {
+  CKS(stage0_filter(K, FilterIn{}));
+  CKS(stage0_survivors(K, false, nullptr));
+  stage0_finish(K);
+  return FQ_OK;
+}
+int stage0_packed(Call &K) {
+  fq_ctx *c = K.c;
+  const fq_packed_batch_t &pb = c->pb;
+  const int slot = c->head_slot;   // chosen by fq_align_packed: the buffer the batch was prefetched into, else a free one (uploaded now)
+  CK(fqdev::compute_wait_copy(slot));
+  FilterIn in;
+  in.head = c->d_head[slot].p; in.len = c->d_hlen[slot].p; in.uniform_len = pb.uniform_len; in.body_stride = pb.body_stride;
+  in.qual_last = c->o.trim_qual >= 1 && pb.qual_last ? c->d_qlast[slot].p : nullptr;
+  CKS(stage0_filter(K, in));
+  const int64_t bulk_min = c->kn.packed_bulk_min >= 0 ? c->kn.packed_bulk_min : (int64_t)K.n / 8;
+  const bool bulk = !c->o.single_end && K.n_surv > 0 && (int64_t)K.n_surv >= bulk_min;   // many survivors: upload the whole body, gather on the device (single-end batches: rows gathered on the host, the absent mates' among them as empty rows)
+  const bool need_crow = bulk && pb.n_exc > 0;   // batch row -> compact row (-1: not unpacked), for the exception list of the whole batch
+  if (need_crow) { CKM(c->d_crow.ensure(K.n2)); CK(fqdev::dfill(c->d_crow.p, 0xff, (size_t)K.n2 * 4)); }
+  CKS(stage0_survivors(K, true, need_crow ? c->d_crow.p : nullptr));
+  CKS(stage0_rows_packed(K, bulk));
+  CKS(stage0_whole_batch(K, in));
+  stage0_finish(K);
+  return FQ_OK;
+}
+int stage0_text(Call &K) {
+  fq_ctx *c = K.c;
+  FilterIn in;
+  in.head = c->tb->d_head; in.len = c->tb->d_hlen; in.uniform_len = c->tb->uniform_len; in.text = c->tb;
+  CKS(stage0_filter(K, in));
+  CKS(stage0_survivors(K, true, nullptr));
+  CKS(stage0_rows_text(K));
+  CKS(stage0_whole_batch(K, in));
   K.trace("  stage0: rows, qualities, names gathered");
-  K.dseq = c->d_seq.p; K.dstride = cstride; K.dlen_trim = c->d_len_trim.p; K.dread_list = c->d_read_list.p;
+  stage0_finish(K);
   return FQ_OK;
 }
 
 // ---- stage A: widths + gap search, tiered by stack-pool size (GPU) ----------------------------------
 // S.aln: concatenated hit lists; per search index s: [aln_off[s], aln_off[s]+aln_n[s])
+// device-filling launches of several contexts take turns (fqdev::device_turn_begin)
+struct Turn { int slots = 1; bool held = false; void take() { if (!held) { fqdev::device_turn_begin(slots); held = true; } } void drop() { if (held) { fqdev::device_turn_end(); held = false; } } ~Turn() { drop(); } };
+// Lpad: exact widths per strand (rows are written 8 positions at a time); Ppad: position records per strand (16-byte aligned rows);
+// nb_need: scores that can occur for the longest read of this call (children may exceed max_diff by one difference)
+struct SearchGeom { int Lpad, Ppad, nb_need; };
+
+bool search_bufs_ensure(SearchBufs &b, size_t nw, const SearchGeom &g, uint32_t aln_cap) {   // room for a launch of nw reads (pools and queue apart: per lane, not per read)
+  return b.work.ensure(nw) && b.wfull.ensure(nw * 2 * g.Lpad) && b.prec.ensure(nw * 2 * g.Ppad) && b.winfo.ensure(nw) && b.bid_end.ensure(nw * 2) && b.order.ensure(nw) &&
+         b.order_cnt.ensure(2 * FQ_ORDER_KEYS + 2) && b.aln.ensure(nw * aln_cap) && b.naln.ensure(nw) && b.status.ensure(nw);
+}
+// widths, position records and start-up words of the reads d_work[0 .. nw) (search indices, on the device) into the set b, and the order
+// in which the search takes them: long searches first (n_hard: fq_order_key)
+int launch_widths(Call &K, SearchBufs &b, const SearchGeom &g, const int32_t *d_work, int nw, int n_hard) {
+  fq_ctx *c = K.c;
+  FqWidthArgs wa{};
+  wa.ix = c->ix->dev; wa.o = c->ko; wa.seq = K.dseq; wa.stride = K.dstride; wa.len_trim = K.dlen_trim; wa.read_list = K.dread_list;
+  wa.work = d_work; wa.n_work = nw; wa.wfull = b.wfull.p; wa.wstride = g.Lpad;
+  wa.prec = b.prec.p; wa.pstride = g.Ppad; wa.winfo = b.winfo.p; wa.maxdiff_lut = c->d_maxdiff.p; wa.bid_end = b.bid_end.p; wa.counters = c->d_counters.p;
+  CK(fqdev::launch_width(wa));
+  CK(fqdev::launch_order(b.bid_end.p, nw, n_hard, b.order.p, b.order_cnt.p));
+  return FQ_OK;
+}
+// what every search launch over the set b has in common; what belongs to a round (the buckets of the round without gap children, skip_bound, refill_min,
+// max_waves, lane_major, seg / n_seg) is set where the round is launched
+FqGapArgs gap_args(fq_ctx *c, const SearchBufs &b, const SearchGeom &g, const FqGapTier &T, int nw) {
+  FqGapArgs ga{};
+  ga.ix = c->ix->dev; ga.o = c->ko; ga.o.n_buckets = g.nb_need; ga.n_work = nw; ga.winfo = b.winfo.p;
+  ga.order = c->kn.gap_no_order ? nullptr : b.order.p; ga.split = c->kn.gap_no_order ? nullptr : b.order_cnt.p + 2 * FQ_ORDER_KEYS;
+  ga.wfull = b.wfull.p; ga.wstride = g.Lpad; ga.prec = b.prec.p; ga.pstride = g.Ppad;
+  ga.pool = b.pool.p; ga.heads = b.heads.p; ga.tier = T; ga.aln = b.aln.p; ga.n_aln = b.naln.p; ga.status = b.status.p;
+  ga.counters = c->d_counters.p; ga.queue = b.queue.p;
+  return ga;
+}
+
+// The hit lists of one launch over the set b (nw reads, wk: their search indices on the host) come to the host and join the call's lists.
+// The packed array holds exactly the lists of the reads that completed, in work order (a failed read reports no hits): it
+// lands behind the lists of the earlier launches, and every read finds its list at the offset the device's prefix sum gave it.
+// room_later: a buffer that has to grow here is given room for the rounds behind this one as well (growing again means copying what it holds).
+// turn: dropped once the launch's kernels have finished.  h_bid (experiment gap_split_hard, else null): the lower bounds of the reads' ends come with the counts.
+// The views hold until the next collection.
+struct HitLists { const uint32_t *status; uint64_t total; };   // per work item: 0 = settled; the hits of the launch
+int collect_hits(Call &K, SearchBufs &b, const int32_t *wk, int nw, uint32_t aln_cap, bool room_later, Turn *turn, uint8_t *h_bid, HitLists *out) {
+  fq_ctx *c = K.c;
+  CK(fqdev::launch_scan(b.naln.p, c->d_off.p, (uint32_t)nw));   // (d_off: sized with the launch's buffers)
+  CKM(c->p_u32a.ensure((size_t)nw + 2) && c->p_u32b.ensure((size_t)nw + 2));
+  uint32_t *h_status = c->p_u32a.p, *h_naln = c->p_u32b.p;
+  CK(fqdev::copy_pinned(h_status, b.status.p, (size_t)nw * 4, 0));
+  CK(fqdev::copy_pinned(h_naln, b.naln.p, (size_t)nw * 4, 0));
+  uint64_t *h_off = (uint64_t *)c->arena.alloc(((size_t)nw + 1) * 8);      // exclusive prefix sums of the hit counts (launch_scan)
+  if (!h_off) { c->err = "out of pinned host memory"; return FQ_ENOMEM; }
+  CK(fqdev::copy_pinned(h_off, c->d_off.p, ((size_t)nw + 1) * 8, 0));
+  if (h_bid) CKS(d2h_staged(c, h_bid, b.bid_end.p, (size_t)nw * 2));
+  CKS(sync_staged(c));
+  if (turn) turn->drop();
+  K.trace("  A: width + search kernels, counts D2H");
+  const uint64_t total = h_off[nw], base = c->st.aln.n;
+  const uint64_t hits_need = base + total + 1, hits_room = room_later ? hits_need + hits_need / 2 : hits_need;
+  CKM(c->d_hits.ensure_keep(c->d_hits.cap >= hits_need ? hits_need : hits_room, base) && c->p_aln.ensure_keep(c->p_aln.cap >= hits_need ? hits_need : hits_room, base));
+  CK(fqdev::launch_pack_aln(b.aln.p, b.naln.p, c->d_off.p, aln_cap, (uint32_t)nw, c->d_hits.p + base));
+  CK(fqdev::launch_aln_index(b.work.p, b.status.p, c->d_off.p, b.naln.p, base, c->d_aoff.p, c->d_an.p, nw));   // the device's own index of the lists (the records stay there)
+  CK(fqdev::copy_pinned(c->p_aln.p + base, c->d_hits.p + base, total * sizeof(FqAln), 0));
+  CKS(sync_staged(c));
+  c->st.aln.p = c->p_aln.p; c->st.aln.n = base + total;
+  K.trace("  A: hit lists D2H");
+  parallel_chunks((size_t)nw, K.host_threads, K.par_min, [&](size_t lo, size_t hi, int) {
+    for (size_t w = lo; w < hi; ++w) {
+      if (h_status[w]) continue;
+      const int s = wk[w];
+      K.aln_off[s] = base + h_off[w];
+      K.aln_n[s] = h_naln[w];
+    }
+  });
+  *out = {h_status, total};
+  return FQ_OK;
+}
+
+// ---- experiment (gap_pipeline_min, off by default): the first round in segments of the (sorted: hard reads first) queue, and what
+//      each segment leaves unsettled searched in full on the context's second stream while the next segment's first round runs.
+//      Measured at 8.4 M reads per call: the search stage takes 93 / 93 / 114 ms with 2 / 4 / 8 segments against 82.6 ms for the two
+//      rounds one after the other -- at this size the second round is no longer a tail but 40 % of the stage's work, its
+//      persistent wavefronts take a quarter of the wave slots for as long as they live, and the first round loses more to that
+//      (it scales with occupancy: 16 -> 12 wavefronts per CU costs it 20 %) than the overlap saves.  Kept, bit-exact and tested.
+// ga: the first round's launch over the context's first set (nw reads); the second rounds use the second set, tier T2.  *n2: reads whose second round ran
+// here (their search indices: the head of the second set's work list); *piped stays false, and nothing was launched, when the second set cannot be had.
+int search_pipelined(Call &K, const SearchGeom &g, FqGapArgs ga, int nw, const FqGapTier &T2, uint32_t *n2, bool *piped) {
+  fq_ctx *c = K.c;
+  SearchBufs &b1 = c->sb[0], &b2 = c->sb[1];
+  const int S = c->kn.gap_pipeline_segs;
+  const size_t cap2 = std::max<size_t>(65536, (size_t)nw / 4);
+  const size_t slots2 = (size_t)fqdev::gap_lane_slots(gap_args(c, b2, g, T2, (int32_t)cap2));
+  *piped = search_bufs_ensure(b2, cap2, g, T2.aln_cap) && c->d_seg_cnt.ensure((size_t)S + 1) && b2.queue.ensure(4) && b2.heads.ensure(slots2 * FQ_MAX_BUCKETS) && b2.pool.ensure(slots2 * T2.pool_cap);
+  if (!*piped) return FQ_OK;
+  uint32_t n2_total = 0;
+  CK(fqdev::dzero(c->d_seg_cnt.p, ((size_t)S + 1) * 4));
+  fqdev::time_begin(FQ_K_GAP);
+  bool room = true;
+  for (int sg = 0; sg < S; ++sg) {
+    ga.seg = sg; ga.n_seg = S;
+    CK(fqdev::launch_gap(ga));
+    if (!room) continue;
+    CK(fqdev::launch_collect(ga.order, ga.split, nw, sg, S, b1.status.p, b1.work.p, b2.work.p + n2_total, c->d_seg_cnt.p + sg));
+    uint32_t cnt = 0;
+    CKS(d2h_staged(c, &cnt, c->d_seg_cnt.p + sg, 4));
+    CKS(sync_staged(c));
+    if ((size_t)n2_total + cnt > cap2) { room = false; continue; }      // (what does not fit stays for the ordinary next round)
+    if (cnt == 0) continue;
+    CK(fqdev::stream_aux(1));
+    CK(fqdev::stream_fork());
+    CKS(launch_widths(K, b2, g, b2.work.p + n2_total, (int)cnt, 0));
+    FqGapArgs gb = gap_args(c, b2, g, T2, (int32_t)cnt);
+    gb.aln += (size_t)n2_total * T2.aln_cap; gb.n_aln += n2_total; gb.status += n2_total;
+    gb.refill_min = 16;
+    CK(fqdev::launch_gap(gb));
+    CK(fqdev::stream_aux(0));
+    n2_total += cnt;
+  }
+  CK(fqdev::stream_join());
+  fqdev::time_end(FQ_K_GAP);
+  *n2 = n2_total;
+  return FQ_OK;
+}
+
 int stageA_search(Call &K) {
   fq_ctx *c = K.c;
-  const fq_index *ix = c->ix;
   const fq_opts_t &o = c->o;
+  SearchBufs &b = c->sb[0];
   const int n_search = K.n_search, max_len_all = K.max_len_all;
   // the hit lists stay where the copy engine lands them (the context's pinned buffer): S.aln is a view of it
   c->st.aln.p = c->p_aln.p; c->st.aln.n = 0;
@@ -1228,16 +1334,14 @@ int stageA_search(Call &K) {
   par_assign(K.aln_n, (size_t)n_search, (uint32_t)0, K.host_threads, K.par_min);
   CKM(c->d_aoff.ensure((size_t)n_search + 1) && c->d_an.ensure((size_t)n_search + 1) && c->d_hits.ensure(1));
   CK(fqdev::dzero(c->d_an.p, ((size_t)n_search + 1) * 4));
-  const int Lpad = (max_len_all + 1 + 7) & ~7;                  // exact widths per strand; rows are written 8 positions at a time
-  const int Ppad = (max_len_all + 1 + FQ_POS_PAD + 7) & ~7;     // position records per strand (16-byte aligned rows)
+  const SearchGeom g = {(max_len_all + 1 + 7) & ~7, (max_len_all + 1 + FQ_POS_PAD + 7) & ~7,
+                        (c->maxdiff_lut[max_len_all] + 1) * o.s_mm + o.max_gapo * o.s_gapo + o.max_gape * o.s_gape + 1};
   // tier 0: one read per lane, bounded stack and pop count; what it gives up on is searched again by one wavefront per read
   // (tier 1 with push-time pruning, tier 2 exactly as the reference: no pruning, n_entries exact).  The wavefront kernel never
   // reuses pool slots, so its pools hold every push of a search, not just the live entries.
   const uint32_t exact_pool = (uint32_t)std::min<uint64_t>(4ull * (uint64_t)o.max_entries + 4096ull, 0x7fffffffull);
   const FqGapTier lane_tier = {c->kn.gap_pool, 32u, 0, 0, c->kn.gap_long_pops, c->kn.gap_long_always, 0, 0};
   const FqGapTier wave_tier = {262144u, 512u, 0, 1, 0u, 0, 0, 0}, exact_tier = {exact_pool, 8192u, 1, 1, 0u, 0, 0, 0};
-  // scores that can occur for the longest read of this call (children may exceed max_diff by one difference)
-  const int nb_need = (c->maxdiff_lut[max_len_all] + 1) * o.s_mm + o.max_gapo * o.s_gapo + o.max_gape * o.s_gape + 1;
   // A launch that fills the device begins with the round that searches without gap children (FqGapLane, NOGAP): the reads it
   // cannot settle are searched in full by the next round.
   vector<FqGapTier> tiers;
@@ -1275,18 +1379,12 @@ int stageA_search(Call &K) {
     for (size_t c0 = 0, step_c = 0; c0 < work.size(); c0 += step_c) {
       step_c = c0 == 0 && first_chunk > 0 ? first_chunk : chunk_reads[tier];
       const int nw = (int)std::min(step_c, work.size() - c0);
-      CKM(c->d_work.ensure(nw) && c->d_wfull.ensure((size_t)nw * 2 * Lpad) && c->d_prec.ensure((size_t)nw * 2 * Ppad) && c->d_winfo.ensure(nw) && c->d_bid_end.ensure((size_t)nw * 2) && c->d_order.ensure(nw) && c->d_order_cnt.ensure(2 * FQ_ORDER_KEYS + 2) &&
-          c->d_aln.ensure((size_t)nw * T.aln_cap) && c->d_naln.ensure(nw) && c->d_status.ensure(nw) && c->d_off.ensure(nw + 1));
-      CKM(c->p_i32.ensure(nw));
-      memcpy(c->p_i32.p, work.data() + c0, (size_t)nw * 4);
-      CK(fqdev::copy_pinned(c->d_work.p, c->p_i32.p, (size_t)nw * 4, 1));
+      const int32_t *wk = work.data() + c0;
+      CKM(search_bufs_ensure(b, (size_t)nw, g, T.aln_cap) && c->d_off.ensure((size_t)nw + 1) && c->p_i32.ensure(nw));   // (d_off: collect_hits, of this launch and of the pipeline's second rounds, at most nw reads)
+      memcpy(c->p_i32.p, wk, (size_t)nw * 4);
+      CK(fqdev::copy_pinned(b.work.p, c->p_i32.p, (size_t)nw * 4, 1));
       c->stats.h2d_bytes += (size_t)nw * 4;
-      FqWidthArgs wa{};
-      wa.ix = ix->dev; wa.o = c->ko; wa.seq = K.dseq; wa.stride = K.dstride; wa.len_trim = K.dlen_trim; wa.read_list = K.dread_list;
-      wa.work = c->d_work.p; wa.n_work = nw; wa.wfull = c->d_wfull.p; wa.wstride = Lpad;
-      wa.prec = c->d_prec.p; wa.pstride = Ppad; wa.winfo = c->d_winfo.p; wa.maxdiff_lut = c->d_maxdiff.p; wa.bid_end = c->d_bid_end.p; wa.counters = c->d_counters.p;
-      // device-filling launches of several contexts take turns (fqdev::device_turn_begin)
-      struct Turn { int slots = 1; bool held = false; void take() { if (!held) { fqdev::device_turn_begin(slots); held = true; } } void drop() { if (held) { fqdev::device_turn_end(); held = false; } } ~Turn() { drop(); } } turn;
+      Turn turn;
       turn.slots = c->kn.device_turn_slots;
       const bool big_call = c->kn.device_turns > 0 && !T.coop && c->kn.gap_nogap_min >= 0 && (int64_t)n_search >= std::max(c->kn.gap_nogap_min, c->kn.device_turn_min) &&
                             (T.nogap || !(c->kn.device_turns == 3 || (c->kn.device_turns == 2 && g_calls_in_flight.load(std::memory_order_relaxed) >= 3)));
@@ -1297,16 +1395,12 @@ int stageA_search(Call &K) {
       K.trace("  A: work list, buffers");
       if (big_call && c->kn.device_turns >= 2) turn.take();
       fqdev::time_begin(FQ_K_WIDTH);
-      CK(fqdev::launch_width(wa));
-      CK(fqdev::launch_order(c->d_bid_end.p, nw, (int)(n_hard > c0 ? std::min<size_t>(n_hard - c0, (size_t)nw) : 0), c->d_order.p, c->d_order_cnt.p));   // long searches first
+      CKS(launch_widths(K, b, g, b.work.p, nw, (int)(n_hard > c0 ? std::min<size_t>(n_hard - c0, (size_t)nw) : 0)));
       fqdev::time_end(FQ_K_WIDTH);
-      FqGapArgs ga{};
-      ga.ix = ix->dev; ga.o = c->ko; ga.o.n_buckets = T.nogap ? std::min(nb_need, o.s_gapo + o.s_mm + 1) : nb_need; /* (no-gap round: parents below s_gapo only) */ ga.n_work = nw; ga.winfo = c->d_winfo.p; ga.order = c->kn.gap_no_order ? nullptr : c->d_order.p; ga.split = c->kn.gap_no_order ? nullptr : c->d_order_cnt.p + 2 * FQ_ORDER_KEYS;
-      ga.wfull = c->d_wfull.p; ga.wstride = Lpad; ga.prec = c->d_prec.p; ga.pstride = Ppad;
-      ga.pool = c->d_pool.p; ga.heads = c->d_heads.p; ga.tier = T; ga.aln = c->d_aln.p; ga.n_aln = c->d_naln.p; ga.status = c->d_status.p;
-      ga.counters = c->d_counters.p; ga.queue = c->d_queue.p;
+      FqGapArgs ga = gap_args(c, b, g, T, nw);
       if (T.nogap) {   // a hit of b mismatches settles a read only if (b + 1) * s_mm < s_gapo (FqGapLane::finish)
-        ga.bid_end = c->d_bid_end.p;
+        ga.o.n_buckets = std::min(g.nb_need, o.s_gapo + o.s_mm + 1);   // (parents below s_gapo only)
+        ga.bid_end = b.bid_end.p;
         // (-1: calls of up to 4 M searched reads, where the next round is all tail and starts its long searches at once anyway; see FqGapArgs::skip_bound)
         ga.skip_bound = c->kn.gap_skip_bound >= 0 ? (int32_t)c->kn.gap_skip_bound : o.s_mm > 0 && n_search <= ((int64_t)4 << 20) ? std::max(1, (o.s_gapo + o.s_mm - 1) / o.s_mm - 1) : 0;
       }
@@ -1321,120 +1415,37 @@ int stageA_search(Call &K) {
       for (;;) {
         const size_t slots = (size_t)fqdev::gap_lane_slots(ga);
         GrowScope as_is(1.0);      // (per lane, not per read)
-        if (c->d_heads.ensure(slots * FQ_MAX_BUCKETS) && c->d_pool.ensure(slots * T.pool_cap)) break;
+        if (b.heads.ensure(slots * FQ_MAX_BUCKETS) && b.pool.ensure(slots * T.pool_cap)) break;
         const int waves = (int)(T.coop ? slots : slots / 64);
         if (waves <= 1) { c->err = "out of device memory for the search pools"; return FQ_ENOMEM; }
         ga.max_waves = waves / 2;
       }
-      ga.pool = c->d_pool.p; ga.heads = c->d_heads.p;
-      // ---- experiment (gap_pipeline_min, off by default): the first round in segments of the (sorted: hard reads first) queue, and what
-      //      each segment leaves unsettled searched in full on the context's second stream while the next segment's first round runs.
-      //      Measured at 8.4 M reads per call: the search stage takes 93 / 93 / 114 ms with 2 / 4 / 8 segments against 82.6 ms for the two
-      //      rounds one after the other -- at this size the second round is no longer a tail but 40 % of the stage's work, its
-      //      persistent wavefronts take a quarter of the wave slots for as long as they live, and the first round loses more to that
-      //      (it scales with occupancy: 16 -> 12 wavefronts per CU costs it 20 %) than the overlap saves.  Kept, bit-exact and tested.
+      ga.pool = b.pool.p; ga.heads = b.heads.p;
       if (big_call) turn.take();
-      uint32_t n2_total = 0;                 // reads whose second round ran in the pipeline
-      vector<uint32_t> seg_cnt;
+      uint32_t n2_total = 0;                 // reads whose second round ran in the pipeline (search_pipelined)
       bool piped = false;
       const FqGapTier T2 = [&] { FqGapTier t = lane_tier; t.long_pops = 0; return t; }();
-      if (T.nogap && c0 == 0 && (size_t)nw == work.size() && c->kn.gap_pipeline_min >= 0 && (int64_t)nw >= c->kn.gap_pipeline_min && nw >= 64 * c->kn.gap_pipeline_segs) {
-        const int S = c->kn.gap_pipeline_segs;
-        const size_t cap2 = std::max<size_t>(65536, (size_t)nw / 4);
-        FqGapArgs g2{};
-        g2.ix = ix->dev; g2.o = c->ko; g2.o.n_buckets = nb_need; g2.tier = T2; g2.n_work = (int32_t)cap2;
-        const size_t slots2 = (size_t)fqdev::gap_lane_slots(g2);
-        piped = c->d_work2.ensure(cap2) && c->d_cnt2.ensure((size_t)S + 1) && c->d_wfull2.ensure(cap2 * 2 * Lpad) && c->d_prec2.ensure(cap2 * 2 * Ppad) && c->d_winfo2.ensure(cap2) &&
-                c->d_bid_end2.ensure(cap2 * 2) && c->d_order2.ensure(cap2) && c->d_order_cnt2.ensure(2 * FQ_ORDER_KEYS + 2) && c->d_aln2.ensure(cap2 * T2.aln_cap) && c->d_naln2.ensure(cap2) &&
-                c->d_status2.ensure(cap2) && c->d_queue2.ensure(4) && c->d_heads2.ensure(slots2 * FQ_MAX_BUCKETS) && c->d_pool2.ensure(slots2 * T2.pool_cap);
-        if (piped) {
-          CK(fqdev::dzero(c->d_cnt2.p, ((size_t)S + 1) * 4));
-          fqdev::time_begin(FQ_K_GAP);
-          bool room = true;
-          for (int sg = 0; sg < S; ++sg) {
-            ga.seg = sg; ga.n_seg = S;
-            CK(fqdev::launch_gap(ga));
-            if (!room) continue;
-            CK(fqdev::launch_collect(ga.order, ga.split, nw, sg, S, c->d_status.p, c->d_work.p, c->d_work2.p + n2_total, c->d_cnt2.p + sg));
-            uint32_t cnt = 0;
-            CKS(d2h_staged(c, &cnt, c->d_cnt2.p + sg, 4));
-            CKS(sync_staged(c));
-            if ((size_t)n2_total + cnt > cap2) { room = false; continue; }      // (what does not fit stays for the ordinary next round)
-            seg_cnt.push_back(cnt);
-            if (cnt == 0) continue;
-            CK(fqdev::stream_aux(1));
-            CK(fqdev::stream_fork());
-            FqWidthArgs w2{};
-            w2.ix = ix->dev; w2.o = c->ko; w2.seq = K.dseq; w2.stride = K.dstride; w2.len_trim = K.dlen_trim; w2.read_list = K.dread_list;
-            w2.work = c->d_work2.p + n2_total; w2.n_work = (int32_t)cnt; w2.wfull = c->d_wfull2.p; w2.wstride = Lpad; w2.prec = c->d_prec2.p; w2.pstride = Ppad;
-            w2.winfo = c->d_winfo2.p; w2.maxdiff_lut = c->d_maxdiff.p; w2.bid_end = c->d_bid_end2.p; w2.counters = c->d_counters.p;
-            CK(fqdev::launch_width(w2));
-            CK(fqdev::launch_order(c->d_bid_end2.p, (int)cnt, 0, c->d_order2.p, c->d_order_cnt2.p));
-            FqGapArgs gb{};
-            gb.ix = ix->dev; gb.o = c->ko; gb.o.n_buckets = nb_need; gb.n_work = (int32_t)cnt; gb.winfo = c->d_winfo2.p;
-            gb.order = c->kn.gap_no_order ? nullptr : c->d_order2.p; gb.split = c->kn.gap_no_order ? nullptr : c->d_order_cnt2.p + 2 * FQ_ORDER_KEYS;
-            gb.wfull = c->d_wfull2.p; gb.wstride = Lpad; gb.prec = c->d_prec2.p; gb.pstride = Ppad; gb.pool = c->d_pool2.p; gb.heads = c->d_heads2.p; gb.tier = T2;
-            gb.aln = c->d_aln2.p + (size_t)n2_total * T2.aln_cap; gb.n_aln = c->d_naln2.p + n2_total; gb.status = c->d_status2.p + n2_total;
-            gb.counters = c->d_counters.p; gb.queue = c->d_queue2.p; gb.refill_min = 16;
-            CK(fqdev::launch_gap(gb));
-            CK(fqdev::stream_aux(0));
-            n2_total += cnt;
-          }
-          CK(fqdev::stream_join());
-          fqdev::time_end(FQ_K_GAP);
-        }
-      }
+      if (T.nogap && c0 == 0 && (size_t)nw == work.size() && c->kn.gap_pipeline_min >= 0 && (int64_t)nw >= c->kn.gap_pipeline_min && nw >= 64 * c->kn.gap_pipeline_segs)
+        CKS(search_pipelined(K, g, ga, nw, T2, &n2_total, &piped));
       if (!piped) {
         fqdev::time_begin(FQ_K_GAP);
         CK(fqdev::launch_gap(ga));
         fqdev::time_end(FQ_K_GAP);
       }
-      CK(fqdev::launch_scan(c->d_naln.p, c->d_off.p, (uint32_t)nw));
-      CKM(c->p_u32a.ensure((size_t)nw + 2) && c->p_u32b.ensure((size_t)nw + 2));
-      uint32_t *h_status = c->p_u32a.p, *h_naln = c->p_u32b.p;
-      uint64_t total = 0;
-      CK(fqdev::copy_pinned(h_status, c->d_status.p, (size_t)nw * 4, 0));
-      CK(fqdev::copy_pinned(h_naln, c->d_naln.p, (size_t)nw * 4, 0));
-      uint64_t *h_off = (uint64_t *)c->arena.alloc(((size_t)nw + 1) * 8);      // exclusive prefix sums of the hit counts (launch_scan)
-      if (!h_off) { c->err = "out of pinned host memory"; return FQ_ENOMEM; }
-      CK(fqdev::copy_pinned(h_off, c->d_off.p, ((size_t)nw + 1) * 8, 0));
       vector<uint8_t> h_bid;
-      if (T.nogap && c->kn.gap_split_hard > 0) { h_bid.resize((size_t)nw * 2); CKS(d2h_staged(c, h_bid.data(), c->d_bid_end.p, (size_t)nw * 2)); }
-      CKS(sync_staged(c));
-      turn.drop();
-      K.trace("  A: width + search kernels, counts D2H");
-      total = h_off[nw];
+      if (T.nogap && c->kn.gap_split_hard > 0) h_bid.resize((size_t)nw * 2);
+      HitLists h;
+      CKS(collect_hits(K, b, wk, nw, T.aln_cap, true, &turn, h_bid.empty() ? nullptr : h_bid.data(), &h));
+      c->stats.d2h_bytes += (size_t)nw * 8 + h.total * sizeof(FqAln);
       if (!h_bid.empty()) {
         bound_of.assign(n_search, 0);
-        for (int w = 0; w < nw; ++w) bound_of[work[c0 + w]] = std::min(h_bid[2 * w], h_bid[2 * w + 1]);
+        for (int w = 0; w < nw; ++w) bound_of[wk[w]] = std::min(h_bid[2 * w], h_bid[2 * w + 1]);
       }
-      // the packed array holds exactly the lists of the reads that completed, in work order (a failed read reports no hits): it
-      // lands behind the lists of the earlier launches, and every read finds its list at the offset the device's prefix sum gave it
-      const uint64_t base = c->st.aln.n;
-      // (a buffer that has to grow here is given room for the rounds behind this one as well: growing again means copying what it holds)
-      const uint64_t hits_need = base + total + 1, hits_room = hits_need + hits_need / 2;
-      CKM(c->d_hits.ensure_keep(c->d_hits.cap >= hits_need ? hits_need : hits_room, base) && c->p_aln.ensure_keep(c->p_aln.cap >= hits_need ? hits_need : hits_room, base));
-      CK(fqdev::launch_pack_aln(c->d_aln.p, c->d_naln.p, c->d_off.p, T.aln_cap, (uint32_t)nw, c->d_hits.p + base));
-      CK(fqdev::launch_aln_index(c->d_work.p, c->d_status.p, c->d_off.p, c->d_naln.p, base, c->d_aoff.p, c->d_an.p, nw));   // the device's own index of the lists (the records stay there)
-      CK(fqdev::copy_pinned(c->p_aln.p + base, c->d_hits.p + base, total * sizeof(FqAln), 0));
-      CKS(sync_staged(c));
-      c->stats.d2h_bytes += (size_t)nw * 8 + total * sizeof(FqAln);
-      c->st.aln.p = c->p_aln.p; c->st.aln.n = base + total;
-      K.trace("  A: hit lists D2H");
-      const int32_t *wk = work.data() + c0;
-      parallel_chunks((size_t)nw, K.host_threads, K.par_min, [&](size_t lo, size_t hi, int) {
-        for (size_t w = lo; w < hi; ++w) {
-          if (h_status[w]) continue;
-          const int s = wk[w];
-          K.aln_off[s] = base + h_off[w];
-          K.aln_n[s] = h_naln[w];
-        }
-      });
       vector<char> in_round2;
       vector<int32_t> list2;
       if (n2_total) {   // the reads whose second round already ran beside the first
         list2.resize(n2_total);
-        CKS(d2h_staged(c, list2.data(), c->d_work2.p, (size_t)n2_total * 4));
+        CKS(d2h_staged(c, list2.data(), c->sb[1].work.p, (size_t)n2_total * 4));
         CKS(sync_staged(c));
         in_round2.assign((size_t)n_search, 0);
         for (int32_t sidx : list2) in_round2[sidx] = 1;
@@ -1446,9 +1457,9 @@ int stageA_search(Call &K) {
         const bool by_class = T.nogap != 0;
         parallel_chunks((size_t)nw, TT, K.par_min, [&](size_t lo, size_t hi, int t) {
           for (size_t w = lo; w < hi; ++w)
-            if (h_status[w]) {
+            if (h.status[w]) {
               ++n_left[(size_t)t * 8];
-              if (in_round2.empty() || !in_round2[wk[w]]) (by_class && !(h_status[w] & FQ_SF_NOHIT) ? left_easy[t] : left[t]).push_back(wk[w]);
+              if (in_round2.empty() || !in_round2[wk[w]]) (by_class && !(h.status[w] & FQ_SF_NOHIT) ? left_easy[t] : left[t]).push_back(wk[w]);
             }
         });
         for (int t = 0; t < TT; ++t) {
@@ -1457,30 +1468,12 @@ int stageA_search(Call &K) {
           next_easy.insert(next_easy.end(), left_easy[t].begin(), left_easy[t].end());
         }
       }
-      if (n2_total) {
-        CK(fqdev::launch_scan(c->d_naln2.p, c->d_off.p, n2_total));
-        uint32_t *st2 = (uint32_t *)c->arena.alloc((size_t)n2_total * 4), *na2 = (uint32_t *)c->arena.alloc((size_t)n2_total * 4);
-        uint64_t *off2 = (uint64_t *)c->arena.alloc(((size_t)n2_total + 1) * 8);
-        if (!st2 || !na2 || !off2) { c->err = "out of pinned host memory"; return FQ_ENOMEM; }
-        CK(fqdev::copy_pinned(st2, c->d_status2.p, (size_t)n2_total * 4, 0));
-        CK(fqdev::copy_pinned(na2, c->d_naln2.p, (size_t)n2_total * 4, 0));
-        CK(fqdev::copy_pinned(off2, c->d_off.p, ((size_t)n2_total + 1) * 8, 0));
-        CKS(sync_staged(c));
-        const uint64_t tot2 = off2[n2_total];
-        const uint64_t base2 = c->st.aln.n;
-        CKM(c->d_hits.ensure_keep(base2 + tot2 + 1, base2) && c->p_aln.ensure_keep(base2 + tot2 + 1, base2));
-        CK(fqdev::launch_pack_aln(c->d_aln2.p, c->d_naln2.p, c->d_off.p, T2.aln_cap, n2_total, c->d_hits.p + base2));
-        CK(fqdev::launch_aln_index(c->d_work2.p, c->d_status2.p, c->d_off.p, c->d_naln2.p, base2, c->d_aoff.p, c->d_an.p, (int)n2_total));
-        CK(fqdev::copy_pinned(c->p_aln.p + base2, c->d_hits.p + base2, tot2 * sizeof(FqAln), 0));
-        CKS(sync_staged(c));
-        c->stats.d2h_bytes += (size_t)n2_total * 20 + tot2 * sizeof(FqAln);
-        c->st.aln.p = c->p_aln.p; c->st.aln.n = base2 + tot2;
-        for (uint32_t t = 0; t < n2_total; ++t) {
-          const int sidx = list2[t];
-          if (st2[t]) { next_work.push_back(sidx); ++c->stats.tier_retries; continue; }
-          K.aln_off[sidx] = base2 + off2[t];
-          K.aln_n[sidx] = na2[t];
-        }
+      if (n2_total) {   // ... and their hit lists; the buffers grow to what these need, nothing comes behind them in this launch
+        HitLists h2;                      // (h's views end here: the collection reuses their staging)
+        CKS(collect_hits(K, c->sb[1], list2.data(), (int)n2_total, T2.aln_cap, false, nullptr, nullptr, &h2));
+        c->stats.d2h_bytes += (size_t)n2_total * 20 + h2.total * sizeof(FqAln);
+        for (uint32_t t = 0; t < n2_total; ++t)
+          if (h2.status[t]) { next_work.push_back(list2[t]); ++c->stats.tier_retries; }
       }
     }
     n_hard = T.nogap ? next_work.size() : 0;
@@ -2453,7 +2446,7 @@ static int packed_check(fq_ctx_t *c, const fq_packed_batch_t *in) {
   if (!in || in->n_pairs < 0 || (in->n_pairs > 0 && (!in->head || !in->body || in->body_stride < 1 || (in->uniform_len <= 0 && !in->len)))) return FQ_EINVAL;
   if (in->n_exc < 0 || (in->n_exc > 0 && !in->exc)) return FQ_EINVAL;
   if (in->n_pairs > c->max_pairs) { c->err = "batch larger than max_pairs_per_batch"; return FQ_ELIMIT; }
-  if (in->uniform_len > 0 && (in->uniform_len < FQ_LMIN || in->uniform_len > FQ_LMAX || (in->uniform_len + 3) / 4 > in->body_stride)) { c->err = "read length outside [" + std::to_string(FQ_LMIN) + "," + std::to_string(FQ_LMAX) + "]"; return FQ_ELIMIT; }
+  if (in->uniform_len > 0 && (in->uniform_len < FQ_LMIN || in->uniform_len > FQ_LMAX || (in->uniform_len + 3) / 4 > in->body_stride)) return refuse_length(c);
   if (c->o.trim_qual >= 1 && in->n_pairs > 0 && (!in->qual || in->qual_stride < 1)) { c->err = "quality trimming needs the batch's qualities"; return FQ_EINVAL; }
   if (in->n_pairs > 0 && in->qual_last && !in->qual) { c->err = "qual_last without the quality rows"; return FQ_EINVAL; }
   if ((in->single_end != 0) != (c->o.single_end != 0)) { c->err = c->o.single_end ? "a single-end context takes single-end batches (fq_pack_single_reads_into)" : "a paired-end context takes paired batches"; return FQ_EINVAL; }
@@ -2565,7 +2558,7 @@ extern "C" int fq_align_text(fq_ctx_t *c, const fq_text_batch *tb, fq_result_bat
   else if (tb->n_pairs > c->max_pairs) { c->err = "batch larger than max_pairs_per_batch"; rc = FQ_ELIMIT; }
   else if ((tb->single_end != 0) != (c->o.single_end != 0)) { c->err = "single-end / paired-end batch on a context of the other kind"; rc = FQ_EINVAL; }
   else if (tb->device != c->ix->device) { c->err = "the batch lives on another device than the context's index"; rc = FQ_EINVAL; }
-  else if (tb->uniform_len > 0 && (tb->uniform_len < FQ_LMIN || tb->uniform_len > FQ_LMAX)) { c->err = "read length outside [" + std::to_string(FQ_LMIN) + "," + std::to_string(FQ_LMAX) + "]"; rc = FQ_ELIMIT; }
+  else if (tb->uniform_len > 0 && (tb->uniform_len < FQ_LMIN || tb->uniform_len > FQ_LMAX)) rc = refuse_length(c);
   if (rc) return broken_stream_call(c, rc);
   if (fqdev::bind(c->dev)) return FQ_ENODEV;
   c->tb = tb;
