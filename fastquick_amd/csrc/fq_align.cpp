@@ -520,6 +520,9 @@ static void fold_counters(const uint64_t *striped, uint64_t *cnt) {
   }
 }
 #define CKS(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0)
+static void dp_take(fq_ctx *c) {   // fq_stats_t::dp_launches: what the launcher just called counted on this thread
+  for (int v = 0; v < FQ_DP_COUNT; ++v) { c->stats.dp_launches[v] += fqdev::dp_launches[v]; fqdev::dp_launches[v] = 0; }
+}
 static int refuse_length(fq_ctx *c) { c->err = "read length outside [" + std::to_string(FQ_LMIN) + "," + std::to_string(FQ_LMAX) + "]"; return FQ_ELIMIT; }
 
 extern "C" int fq_batch_upload(fq_ctx_t *c, const fq_read_batch_t *in) {
@@ -1862,7 +1865,9 @@ int stageC_mate_sw(Call &K) {
         a.ix = ix->dev; a.seq = K.dseq; a.stride = K.dstride; a.len_trim = K.dlen_trim; a.task = c->d_swtask.p; a.n_task = nt;
         a.out = c->d_swout.p; a.cigar = c->d_cig.p; a.cig_cap = cig_cap; a.scratch = c->d_scratch.p; a.scratch_stride = sstride; a.RL = RL; a.QL = QL;
         fqdev::time_begin(FQ_K_SW);
-        CK(big ? fqdev::launch_sw_serial(a) : fqdev::launch_sw(a));
+        const int rc_sw = big ? fqdev::launch_sw_serial(a) : fqdev::launch_sw(a);
+        dp_take(c);      // (before any return: a count never stays behind on the thread for the next context it serves)
+        CK(rc_sw);
         fqdev::time_end(FQ_K_SW);
         CKS(d2h_staged(c, sub_out.data() + t0, c->d_swout.p, (size_t)nt * sizeof(FqSwOut)));
         CKS(d2h_staged(c, sub_cig.data() + t0 * cig_cap, c->d_cig.p, (size_t)nt * cig_cap * 2));
@@ -1973,7 +1978,9 @@ int stageD_refine(Call &K) {
       a.ix = ix->dev; a.seq = K.dseq; a.stride = K.dstride; a.len_trim = K.dlen_trim; a.task = c->d_reftask.p + t0; a.n_task = nt;
       a.out = c->d_refout.p + t0; a.cigar = c->d_cigs.p + K.cig_used + t0 * FQ_CIG_CAP; a.cig_cap = FQ_CIG_CAP; a.scratch = c->d_scratch.p; a.scratch_stride = sstride; a.RL = max_ref; a.QL = max_q;
       fqdev::time_begin(FQ_K_REFINE);
-      CK(fqdev::launch_refine(a));
+      const int rc_ref = fqdev::launch_refine(a);
+      dp_take(c);
+      CK(rc_ref);
       fqdev::time_end(FQ_K_REFINE);
     }
     REC(FQ_ROP_REF_APPLY, nt_all);

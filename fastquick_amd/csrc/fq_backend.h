@@ -62,6 +62,9 @@ int copy_flush_now();                    // launches the small copy_pinned copie
 void time_begin(int kid);
 void time_end(int kid);
 void time_collect(double ms[], uint64_t launches[], int n_ids);   // after sync(); resets the pending list
+// launches of the DP kernels per variant (FQ_DP_*), counted by the launchers of a backend that has variants and taken by the calling
+// thread right behind each launch (fq_align.cpp: dp_take); a backend with one loop per DP leaves them alone
+inline thread_local uint64_t dp_launches[FQ_DP_COUNT] = {};
 
 // launchers (asynchronous on the backend's stream unless stated)
 int launch_prep(const FqPrepArgs &a);

@@ -1551,6 +1551,7 @@ int launch_sw(const FqSwArgs &a) {
   kernel_events(FQ_K_SW_KERNEL, &e0, &e1);
   hipExtLaunchKernelGGL(k_sw_wave, dim3((unsigned)a.n_task), dim3(64), lds, g_stream, e0, e1, 0, b);
   FQ_HIP(hipGetLastError());
+  ++dp_launches[b.trace_in_lds ? FQ_DP_SW_WAVE_LDS : FQ_DP_SW_WAVE_GLOBAL];
   return 0;
 }
 __global__ void __launch_bounds__(64) k_sw_thread(FqSwArgs a) {
@@ -1564,6 +1565,7 @@ int launch_sw_serial(const FqSwArgs &a) {
   kernel_events(FQ_K_SW_KERNEL, &e0, &e1);
   hipExtLaunchKernelGGL(k_sw_thread, dim3(nblk((uint64_t)a.n_task, 64)), dim3(64), 0, g_stream, e0, e1, 0, a);
   FQ_HIP(hipGetLastError());
+  ++dp_launches[FQ_DP_SW_THREAD];
   return 0;
 }
 int launch_refine(const FqRefineArgs &a) {
@@ -1578,6 +1580,7 @@ int launch_refine(const FqRefineArgs &a) {
   if (wave_lds <= 64 * 1024 && !no_wave) {
     hipExtLaunchKernelGGL(k_refine_wave, dim3((unsigned)a.n_task), dim3(64), wave_lds, g_stream, e0, e1, 0, a);
     FQ_HIP(hipGetLastError());
+    ++dp_launches[FQ_DP_REFINE_WAVE];
     return 0;
   }
   const size_t lds = (size_t)3 * (a.RL + 1) * 64 * 4;
@@ -1587,6 +1590,7 @@ int launch_refine(const FqRefineArgs &a) {
     hipExtLaunchKernelGGL(k_refine, dim3(nblk((uint64_t)a.n_task, 64)), dim3(64), 0, g_stream, e0, e1, 0, a);
   }
   FQ_HIP(hipGetLastError());
+  ++dp_launches[lds <= kLdsBudget ? FQ_DP_REFINE_LDS : FQ_DP_REFINE];
   return 0;
 }
 

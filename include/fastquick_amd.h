@@ -484,6 +484,14 @@ int64_t fq_sam_device_bytes(const fq_ctx_t *c);
 #define FQ_K_REC_KERNEL 14   /* the record stages (fq_records.h): set-up, main hit, pairing, XA, task lists, flattening */
 #define FQ_K_EMIT 15         /* the consumers' kernels (fq_emit.h): SAM text, StatCollector's sums */
 #define FQ_K_COUNT 16
+/* which kernel a DP launch went to (fq_stats_t::dp_launches): chosen by the launcher from the batch's largest window and query */
+#define FQ_DP_REFINE_WAVE 0    /* k_refine_wave: a task per wavefront, row arrays and the two-cells-per-byte trace in LDS */
+#define FQ_DP_REFINE_LDS 1     /* k_refine_lds: a task per lane, row arrays in LDS (tuning key refine_lanes only) */
+#define FQ_DP_REFINE 2         /* k_refine: a task per lane out of global scratch */
+#define FQ_DP_SW_WAVE_LDS 3    /* k_sw_wave with the trace matrix in LDS */
+#define FQ_DP_SW_WAVE_GLOBAL 4 /* k_sw_wave with the trace matrix in the task's global scratch */
+#define FQ_DP_SW_THREAD 5      /* k_sw_thread: windows above sw_wave_max */
+#define FQ_DP_COUNT 6
 typedef struct {
   double kernel_ms[FQ_K_COUNT];
   uint64_t kernel_launches[FQ_K_COUNT];
@@ -508,6 +516,7 @@ typedef struct {
   uint64_t host_pairs;          /* both-mapped pairs the host paired (Q6 intervals, many rows): pairs_on_device counts the others */
   double device_wait_ms;        /* time the calls' threads slept waiting for the device (host_ms_* exclude the waits inside their sections) */
   double host_cpu_ms;           /* CPU time the calls' own threads used, set-up to result arrays (the pooled workers of the few parallel passes not included) */
+  uint64_t dp_launches[FQ_DP_COUNT];   /* launches of the mate-rescue and refinement DP per kernel variant (FQ_DP_*); zero on a backend without variants */
 } fq_stats_t;
 void fq_stats_get(const fq_ctx_t *c, fq_stats_t *out);
 void fq_stats_reset(fq_ctx_t *c);

@@ -42,7 +42,11 @@ for seed in range(args.start, args.start + args.seeds):
         il13 = rnd.random() < 0.25
         trim = rnd.random() < 0.4
         ragged = rnd.random() < 0.5
-        rb = synth.make_reads(ref, n, read_len=150, on_target=rnd.choice([0.6, 0.95]), seed=8000 + seed, sub_rate=rnd.choice([0.005, 0.03]),
+        # the length from a generator of its own: the other draws of a seed stay what they were.  (256: the longest read the reference sustains)
+        L = random.Random(seed * 7919 + 13).choice([150, 150, 250, 256])
+        len_args = [] if L == 150 else ["--read_len", str(L + 1)]      # the reference sizes its buffers from it
+        rb = synth.make_reads(ref, n, read_len=L, frag_mean=350.0 if L == 150 else L + 180.0,      # (350: make_reads' default)
+                              on_target=rnd.choice([0.6, 0.95]), seed=8000 + seed, sub_rate=rnd.choice([0.005, 0.03]),
                               del_frac=0.06, ins_frac=0.05, chimera_frac=rnd.choice([0.0, 0.15]), n_rate=0.003, qual_decay=trim)
         single_batch = batch > n                     # differently named mates survive the reference's name check only then
         mate_names = single_batch and rnd.random() < 0.6
@@ -55,7 +59,7 @@ for seed in range(args.start, args.start + args.seeds):
             for i in range(n):
                 ln = int(rb.lens[end, i])
                 if ragged:
-                    ln = random.Random(seed * 1000003 + end * 7919 + i).randint(lo, 150)
+                    ln = random.Random(seed * 1000003 + end * 7919 + i).randint(lo, L)
                 s = rb.seq[end, i, :ln].tobytes()
                 q = rb.qual[end, i, :ln].tobytes()
                 if il13:
@@ -77,7 +81,7 @@ for seed in range(args.start, args.start + args.seeds):
             with gzip.open(path, "wb", compresslevel=1) as fh:
                 fh.write(b"".join(out))
             fq.append(path)
-        extra, cli = ["--batch", str(batch)], ["--batch_pairs", str(batch), "--chunk_pairs", str(batch * rnd.choice([1, 2, 3]))]
+        extra, cli = ["--batch", str(batch)] + len_args, len_args + ["--batch_pairs", str(batch), "--chunk_pairs", str(batch * rnd.choice([1, 2, 3]))]
         if trim:
             extra += ["--q", "15"]; cli += ["--q", "15"]
         if il13:
@@ -96,6 +100,6 @@ for seed in range(args.start, args.start + args.seeds):
             ok = sam_cols(run.stdout, ragged) == sam_cols(want, ragged)
             why = "" if ok else "SAM text differs"
     bad += 0 if ok else 1
-    print("seed %4d n %3d batch %4d %s%s%s%s names=%s%s %s %.1fs %s" % (seed, n, batch, "ragged(%d) " % lo if ragged else "", "q15 " if trim else "", "I " if il13 else "",
+    print("seed %4d len %3d n %3d batch %4d %s%s%s%s names=%s%s %s %.1fs %s" % (seed, L, n, batch, "ragged(%d) " % lo if ragged else "", "q15 " if trim else "", "I " if il13 else "",
                                                                        "wrap " if wrap else "", name_style, "+mate" if mate_names else "", "OK  " if ok else "FAIL", time.time() - t0, why), flush=True)
 sys.exit(1 if bad else 0)

@@ -41,7 +41,7 @@ import ctypes as C  # noqa: E402
 
 def make_pair(rng, n, odd_at):
     ragged = rng.random() < 0.5
-    base_len = int(rng.choice([36, 76, 100, 150, 151, 250]))
+    base_len = int(rng.choice([36, 76, 100, 150, 151, 250, 300, 400, 500]))
     texts = [[], []]
     for i in range(n):
         L = int(rng.integers(max(20, base_len - 60), base_len + 1)) if ragged and rng.random() < 0.4 else base_len
@@ -66,7 +66,7 @@ def make_pair(rng, n, odd_at):
 
 
 def host_path(fq, B, slot_mode):
-    files = [api.FastqFile(p, threads=2, batch_pairs=B, slot_mode=slot_mode, stride=256, name_stride=304, lib=lib) for p in fq]
+    files = [api.FastqFile(p, threads=2, batch_pairs=B, slot_mode=slot_mode, stride=512, name_stride=304, lib=lib) for p in fq]
     rows, err = [], None
     try:
         rows = [f.read(1 << 20) for f in files]
@@ -85,7 +85,7 @@ def host_path(fq, B, slot_mode):
 
 
 def device_path(fq, B, chunk, slot_mode):
-    fe = api.DeviceFrontEnd(fq[0], fq[1], batch_pairs=B, chunk_pairs=chunk, slot_mode=slot_mode, max_read_len=256, lib=lib)
+    fe = api.DeviceFrontEnd(fq[0], fq[1], batch_pairs=B, chunk_pairs=chunk, slot_mode=slot_mode, max_read_len=512, lib=lib)
     heads, lens, names, total = [[], []], [[], []], [[], []], 0
     err = None
     try:
@@ -101,7 +101,7 @@ def device_path(fq, B, chunk, slot_mode):
             fe.release(b)
             total += n
         if n == api.FQ_EFALLBACK:
-            readers = fe.handover(threads=2, stride=256, name_stride=304)
+            readers = fe.handover(threads=2, stride=512, name_stride=304)
             try:
                 rest = [r.read(1 << 20) for r in readers]
             finally:

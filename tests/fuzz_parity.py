@@ -13,7 +13,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--seeds", type=int, default=20)
 ap.add_argument("--start", type=int, default=0)
 ap.add_argument("--adversarial", action="store_true", help="tiny, repeat-rich references and error-rich reads: edge and tie-breaking cases")
-ap.add_argument("--ragged", action="store_true", help="reads of mixed length, 96 bp or more")
+ap.add_argument("--ragged", action="store_true", help="reads of mixed length up to 500 bases (96 or more on even seeds)")
 ap.add_argument("--se", action="store_true", help="single-end contexts (fq_opts_t::single_end) against the oracle's single-end mapper")
 args = ap.parse_args()
 lib = api.load_library()
@@ -26,7 +26,9 @@ for seed in range(args.start, args.start + args.seeds):
     refkw["n_long"] = min(refkw["n_long"], refkw["n_markers"])
     if args.adversarial:
         refkw.update(n_markers=rnd.choice([3, 5, 8]), n_long=rnd.choice([0, 1]), repeat_every=rnd.choice([1, 2, 3]), tandem_every=rnd.choice([0, 2, 5]))
-    read_len = rnd.choice([150, 150, 250]) if args.ragged else rnd.choice([76, 100, 150, 150, 250])
+    read_len = rnd.choice([150, 150, 250, 300, 400, 500]) if args.ragged else rnd.choice([76, 100, 150, 150, 250, 300, 400, 500])
+    if read_len > 250:      # a fragment of such reads fits the long flank alone (2 x 1000 + 1 bases)
+        refkw["n_long"] = refkw["n_markers"]
     readkw = dict(read_len=read_len, on_target=rnd.choice([0.5, 0.9, 1.0]), seed=2000 + seed, sub_rate=rnd.choice([0.005, 0.02, 0.04]),
                   del_frac=rnd.choice([0.0, 0.05, 0.1]), ins_frac=rnd.choice([0.0, 0.05, 0.1]), n_rate=rnd.choice([0.0, 0.003, 0.01]),
                   indel_len_max=rnd.choice([1, 2, 3]), chimera_frac=rnd.choice([0.0, 0.05, 0.2]), qual_decay=rnd.random() < 0.4)
@@ -34,6 +36,8 @@ for seed in range(args.start, args.start + args.seeds):
         readkw.update(on_target=1.0, sub_rate=rnd.choice([0.01, 0.03, 0.06]), del_frac=rnd.choice([0.1, 0.2]), ins_frac=rnd.choice([0.1, 0.2]), chimera_frac=rnd.choice([0.1, 0.3]))
     if read_len < 150:
         readkw.update(frag_mean=read_len + 120, frag_sd=20)
+    elif read_len > 250:
+        readkw.update(frag_mean=read_len + 250)
     okw = {}
     if readkw["qual_decay"]:
         okw["trim_qual"] = 15

@@ -59,6 +59,18 @@ CASES = {
     "long250": (dict(n_markers=12, n_long=3, seed=106),
                 dict(read_len=250, on_target=0.9, seed=206, sub_rate=0.01, del_frac=0.06, ins_frac=0.05, indel_len_max=3,
                      chimera_frac=0.08, frag_mean=430, frag_sd=30), 160, 160, 0),
+    # 256 bases: the longest read the reference sustains (its StatCollector counts cycles in tables of 256 entries and writes behind them for a longer
+    # mapped read, src/StatCollector.cpp:267-274, 314) -- rows wider than 256 bytes, 4 full stripes of the mate-rescue kernel,
+    # the last entry of the cycle tables.  Every marker has the long flank, so that the windows hold a fragment; indels and chimeras give
+    # refinement and mate rescue their tasks.  Lengths up to 500 are held to the oracle (tests/test_read_lengths.py).
+    "long256": (dict(n_markers=6, n_long=6, seed=111),
+                dict(read_len=256, on_target=0.9, seed=211, sub_rate=0.01, del_frac=0.06, ins_frac=0.05, indel_len_max=3,
+                     chimera_frac=0.08, frag_mean=506, frag_sd=30), 120, 120, 0),
+    # ragged rows at the lengths the reference sustains: a length per read from 251 to 256 (`ragged`: lo, hi, seed), decaying qualities with --q 15, so
+    # that the trimmed lengths are ragged too; two batches, each in its own set of read slots
+    "ragged256": (dict(n_markers=6, n_long=6, seed=112),
+                  dict(read_len=256, on_target=0.9, seed=212, sub_rate=0.01, del_frac=0.06, ins_frac=0.05, indel_len_max=3,
+                       chimera_frac=0.08, frag_mean=506, frag_sd=30, qual_decay=True, ragged=(251, 256, 312)), 160, 80, 15),
 }
 # Real reads: the 251 pairs of 151 bp (one of 137 bp; lower-case bases, Illumina names with comments, real quality strings) that
 # the reference ships as its own example input (example/fq.test.list).  The reference FASTA its example.sh names is not in the
@@ -229,7 +241,7 @@ def sparse_to_npz(path_sparse: str, path_npz: str) -> None:
     np.savez_compressed(path_npz, **arrs)
 
 
-SE_CASES = ("basic", "repeat", "trim76", "edge", "long250", "nref", "example151")
+SE_CASES = ("basic", "repeat", "trim76", "edge", "long250", "long256", "nref", "example151")
 SE_CONSUMER_CASES = ("basic", "trim76", "edge")
 
 
@@ -315,7 +327,10 @@ def main() -> None:
                 n_front, times = rkw.pop("front_weight")
                 sel = np.concatenate([np.tile(np.arange(n_front), times), np.arange(n_front, len(ref.marker_pos))])
                 read_ref = synth.SynthRef(ref.names, ref.seqs, ref.genome, ref.marker_pos[sel], ref.flank[sel])
+            ragged = rkw.pop("ragged", None)
             rb = synth.make_reads(read_ref, n, **rkw)
+            if ragged:      # the FASTQ records end at the drawn length
+                rb.lens[:] = np.random.default_rng(ragged[2]).integers(ragged[0], ragged[1] + 1, rb.lens.shape)
             f1, f2 = rb.write_fastq(os.path.join(tmp, "reads"))
             args = ["--batch", batch] + (["--q", q] if q else []) + (["--read_len", readkw["read_len"] + 1] if readkw.get("read_len", 150) > 150 else [])
             ob.run_reference(pre, f1, f2, os.path.join(tmp, "ref_out"), "--genome_size", len(ref.genome), *args)

@@ -161,6 +161,11 @@ def bgzf_pair(g, tmp, level=6, member=3000):
     return out
 
 
+def case_stride(g):
+    """the row stride of a case's reads: its longest read (qc_read_len - 1) rounded up to 16 bytes, 256 at least"""
+    return max(256, (g["qc_read_len"] + 15) // 16 * 16)
+
+
 def run_front_end(lib, g, fq, stages, sam, chunk_batches=2, slot_mode=0, max_read_len=None, se=False, device=0):
     max_len = max_read_len or max(160, (g["qc_read_len"] + 15) // 16 * 16)
     fe = api.DeviceFrontEnd(fq[0], None if se else fq[1], batch_pairs=g["batch"], chunk_pairs=chunk_batches * g["batch"], slot_mode=slot_mode, max_read_len=max_len, device=device, lib=lib)
@@ -249,8 +254,8 @@ def test_front_end_arrays_are_the_host_readers_and_packers(tag, slot_mode, golde
     g = golden_cases[tag]
     fq = bgzf_pair(g, tmp_path, level=1, member=5000)
     B = 64
-    n, head, lens, names = host_arrays(lib, fq, B, slot_mode, stride=256)
-    end, total, dh, dl, dn, fe = front_end_arrays(lib, fq, B, 3 * B, slot_mode)
+    n, head, lens, names = host_arrays(lib, fq, B, slot_mode, stride=case_stride(g))
+    end, total, dh, dl, dn, fe = front_end_arrays(lib, fq, B, 3 * B, slot_mode, max_read_len=case_stride(g))
     fe.close()
     assert end == 0 and total == n == g["n_pairs"]
     for e in range(2):
@@ -285,10 +290,10 @@ def test_front_end_hands_over_at_a_reference_batch_boundary(overlap, golden_case
         with open(path, "wb") as fh:
             fh.write(synth.bgzf_compress(b"\n".join(out) + b"\n", threads=2, level=6, member=4000))
         fq.append(path)
-    n, head, lens, names = host_arrays(lib, fq, B, 0)
-    end, total, dh, dl, dn, fe = front_end_arrays(lib, fq, B, 2 * B, 0)
+    n, head, lens, names = host_arrays(lib, fq, B, 0, stride=case_stride(g))
+    end, total, dh, dl, dn, fe = front_end_arrays(lib, fq, B, 2 * B, 0, max_read_len=case_stride(g))
     assert end == api.FQ_EFALLBACK and total == odd // B * B
-    readers = fe.handover(threads=2, stride=256, name_stride=304)
+    readers = fe.handover(threads=2, stride=case_stride(g), name_stride=304)
     rest = [r.read(1 << 20) for r in readers]
     for r in readers:
         r.close()
@@ -353,9 +358,9 @@ def test_carriage_returns_are_the_references_refusal(golden_cases, lib, tmp_path
         with open(path, "wb") as fh:
             fh.write(synth.bgzf_compress(text, threads=2, level=6, member=4000))
         fq.append(path)
-    end, total, dh, dl, dn, fe = front_end_arrays(lib, fq, B, 2 * B, 0)
+    end, total, dh, dl, dn, fe = front_end_arrays(lib, fq, B, 2 * B, 0, max_read_len=case_stride(g))
     assert end == api.FQ_EFALLBACK and total == odd // B * B
-    readers = fe.handover(threads=2, stride=256, name_stride=304)
+    readers = fe.handover(threads=2, stride=case_stride(g), name_stride=304)
     with pytest.raises(api.FastquickError, match="this fastq file contains reads with different length"):
         readers[0].read(1 << 20)
     for r in readers:
@@ -402,7 +407,7 @@ def test_closing_in_the_middle_of_a_stream_does_not_hang(golden_cases, lib, tmp_
     g = golden_cases["qc"]
     fq = bgzf_pair(g, tmp_path, level=1, member=2000)
     for take in (1, 0):
-        fe = api.DeviceFrontEnd(fq[0], fq[1], batch_pairs=64, chunk_pairs=64, slot_mode=0, max_read_len=256, lib=lib)
+        fe = api.DeviceFrontEnd(fq[0], fq[1], batch_pairs=64, chunk_pairs=64, slot_mode=0, max_read_len=case_stride(g), lib=lib)
         for _ in range(take):
             n, b = fe.next()
             assert n == 64
