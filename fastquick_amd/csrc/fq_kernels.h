@@ -2059,86 +2059,69 @@ struct FqRowsPlanar {
   FQ_HD void set(int i, const FqCell &v) const { M[i * stride] = v.M; I[i * stride] = v.I; D[i * stride] = v.D; }
 };
 
-// Banded global alignment with end-gap penalty (aln_global_core, stdaln.c:345-525).  s1/s2 are
-// 0-based code arrays; R holds len1+1 cells (single row, updated in place: the cell above is read
-// before it is overwritten, the diagonal one is carried in registers); trace = (len2+1)*(len1+1)
-// bytes.  ops receives the path (end -> start), returns score, *n_ops = path_len, (*fi,*fj) =
-// coordinates of the last path element (path[path_len-1]).  Band geometry, edge rules (set_end_I /
-// set_end_D, "I = -inf" on the band's right edge) and move precedence follow the reference exactly.
-template <class Rows>
-FQ_HD int fq_global_align(const uint8_t *s1, int len1, const uint8_t *s2, int len2, int band, int gap_end, const Rows &R,
-                          uint8_t *trace, uint8_t *ops, int *n_ops, int *fi, int *fj) {
-  if (len1 == 0 || len2 == 0) { *n_ops = 0; return 0; }
-  int b1, b2;
-  if (len1 > len2) { b1 = len1 - len2 + band; b2 = band; } else { b1 = band; b2 = len2 - len1 + band; }
-  if (b1 > len1) b1 = len1;
-  if (b2 > len2) b2 = len2;
-  const int W = len1 + 1;
-  const int end_ext = gap_end >= 0 ? gap_end : FQ_GAP_E;
+// Banded global alignment with end-gap penalty (aln_global_core, stdaln.c:345-525).  Band geometry, edge rules (set_end_I /
+// set_end_D, "I = -inf" on the band's right edge) and move precedence follow the reference exactly; they are stated once, here,
+// for the serial fill below and the wavefront fill (fq_global_align_wave, fq_device.hip).
+struct FqBand { int len1, len2, b1, b2, W, end_ext, p1_end; };
+FQ_HD FqBand fq_band(int len1, int len2, int band, int gap_end) {
+  FqBand g;
+  g.len1 = len1; g.len2 = len2;
+  if (len1 > len2) { g.b1 = len1 - len2 + band; g.b2 = band; } else { g.b1 = band; g.b2 = len2 - len1 + band; }
+  if (g.b1 > len1) g.b1 = len1;
+  if (g.b2 > len2) g.b2 = len2;
+  g.W = len1 + 1;
+  g.end_ext = gap_end >= 0 ? gap_end : FQ_GAP_E;
+  g.p1_end = g.b2 < len2 ? g.b2 : len2 - 1;
+  return g;
+}
+// row j's cells are columns c0 + 1 .. hi; column c0 is the "left" initialisation; endI: the cell at hi has an I at all (set_end_I)
+struct FqBandRow { int phase, c0, hi; bool p15, endI, endD; };
+FQ_HD FqBandRow fq_band_row(const FqBand &g, int j) {
+  const int len1 = g.len1, len2 = g.len2, b1 = g.b1, b2 = g.b2;
+  FqBandRow r;
+  if (j <= g.p1_end) r.phase = 1;
+  else if (j == g.p1_end + 1 && j == len2 && b2 != len2 - 1) r.phase = 5;   // "last row for part 1"
+  else if (j <= len2 - b2 + 1) r.phase = 2;
+  else if (j < len2) r.phase = 3;
+  else r.phase = 4;
+  r.p15 = r.phase == 1 || r.phase == 5; r.endD = r.phase == 5 || r.phase == 4;
+  r.c0 = r.p15 ? 0 : j - b2;
+  r.hi = (r.p15 ? j + b1 <= len1 + 1 : r.phase == 2) ? j + b1 - 1 : len1;
+  r.endI = r.p15 ? j + b1 - 1 > len1 : r.phase != 2;
+  return r;
+}
+FQ_HD FqCell fq_band_row0(const FqBand &g, const FqCell &left, uint8_t &tb) {   // row 0, columns 1 .. b1 - 1
+  FqCell c;
   uint8_t fm;
-  {
-    FqCell left;
-    left.M = 0; left.I = left.D = FQ_NEG_INF;
-    R.set(0, left);
-    for (int i = 1; i < b1; ++i) {
-      FqCell c;
-      c.M = c.I = FQ_NEG_INF;
-      c.D = fq_pick_gap(left.M, left.D, end_ext, fm);
-      trace[i] = (uint8_t)(fm ? 0 : 8);
-      R.set(i, c);
-      left = c;
-    }
-  }
-  const int p1_end = b2 < len2 ? b2 : len2 - 1;
-  for (int j = 1; j <= len2; ++j) {
-    int phase;
-    if (j <= p1_end) phase = 1;
-    else if (j == p1_end + 1 && j == len2 && b2 != len2 - 1) phase = 5;   // "last row for part 1"
-    else if (j <= len2 - b2 + 1) phase = 2;
-    else if (j < len2) phase = 3;
-    else phase = 4;
-    const int c2 = s2[j - 1];
-    uint8_t *tr = trace + (size_t)j * (size_t)W;
-    const bool endD = (phase == 5 || phase == 4);
-    int lo, hi;
-    FqCell diag, left;
-    if (phase == 1 || phase == 5) {
-      lo = 1; hi = (j + b1 <= len1 + 1) ? j + b1 - 1 : len1;
-      diag = R.get(0);
-      left.M = left.D = FQ_NEG_INF;
-      left.I = fq_pick_gap(diag.M, diag.I, end_ext, fm);
-      tr[0] = (uint8_t)(fm ? 0 : 4);
-      R.set(0, left);
-    } else {
-      lo = j - b2 + 1; hi = (phase == 2) ? j + b1 - 1 : len1;
-      diag = R.get(j - b2);
-      left.M = left.I = left.D = FQ_NEG_INF;
-      R.set(j - b2, left);
-    }
-    for (int i = lo; i <= hi; ++i) {
-      const FqCell up = R.get(i);
-      FqCell c;
-      uint8_t tM, tb;
-      c.M = fq_pick_M(diag, fq_sm_maq(s1[i - 1], c2), tM);
-      tb = tM;
-      if (i != hi) { c.I = fq_pick_gap(up.M, up.I, FQ_GAP_E, fm); tb |= (uint8_t)(fm ? 0 : 4); }
-      else if (phase == 1 || phase == 5) {
-        if (j + b1 - 1 > len1) { c.I = fq_pick_gap(up.M, up.I, end_ext, fm); tb |= (uint8_t)(fm ? 0 : 4); }
-        else c.I = FQ_NEG_INF;
-      } else if (phase == 2) c.I = FQ_NEG_INF;
-      else { c.I = fq_pick_gap(up.M, up.I, end_ext, fm); tb |= (uint8_t)(fm ? 0 : 4); }
-      c.D = fq_pick_gap(left.M, left.D, endD ? end_ext : FQ_GAP_E, fm);
-      tb |= (uint8_t)(fm ? 0 : 8);
-      tr[i] = tb;
-      R.set(i, c);
-      diag = up;
-      left = c;
-    }
-  }
-  // traceback (stdaln.c:484-512)
-  const FqCell last = R.get(len1);
+  c.M = c.I = FQ_NEG_INF;
+  c.D = fq_pick_gap(left.M, left.D, g.end_ext, fm);
+  tb = (uint8_t)(fm ? 0 : 8);
+  return c;
+}
+FQ_HD FqCell fq_band_left(const FqBand &g, const FqBandRow &r, const FqCell &up, uint8_t &tb) {   // column c0
+  FqCell c;
+  uint8_t fm;
+  c.M = c.I = c.D = FQ_NEG_INF;
+  tb = 0;
+  if (r.p15) { c.I = fq_pick_gap(up.M, up.I, g.end_ext, fm); tb = (uint8_t)(fm ? 0 : 4); }
+  return c;
+}
+FQ_HD FqCell fq_band_cell(const FqBand &g, const FqBandRow &r, int i, const FqCell &diag, const FqCell &up, const FqCell &left, int sc, uint8_t &tb) {
+  FqCell c;
+  uint8_t fm;
+  c.M = fq_pick_M(diag, sc, tb);
+  if (i != r.hi || r.endI) { c.I = fq_pick_gap(up.M, up.I, i != r.hi ? FQ_GAP_E : g.end_ext, fm); tb |= (uint8_t)(fm ? 0 : 4); }
+  else c.I = FQ_NEG_INF;
+  c.D = fq_pick_gap(left.M, left.D, r.endD ? g.end_ext : FQ_GAP_E, fm);
+  tb |= (uint8_t)(fm ? 0 : 8);
+  return c;
+}
+// traceback (stdaln.c:484-512) from the last cell; get(j, i) is cell (j, i)'s trace.  ops receives the path (end -> start), returns
+// the score, *n_ops = path_len, (*fi,*fj) = coordinates of the last path element (path[path_len-1])
+template <class Get>
+FQ_HD int fq_traceback(Get get, int len1, int len2, const FqCell &last, uint8_t *ops, int *n_ops, int *fi, int *fj) {
   int i = len1, j = len2, mx = last.M;
-  uint8_t tb = trace[(size_t)j * W + i];
+  uint8_t tb = get(j, i);
   int type = tb & 3, ctype = FQ_OP_M;
   if (last.I > mx) { mx = last.I; type = (tb & 4) ? FQ_OP_I : FQ_OP_M; ctype = FQ_OP_I; }
   if (last.D > mx) { mx = last.D; type = (tb & 8) ? FQ_OP_D : FQ_OP_M; ctype = FQ_OP_D; }
@@ -2147,13 +2130,43 @@ FQ_HD int fq_global_align(const uint8_t *s1, int len1, const uint8_t *s2, int le
   do {
     if (ctype == FQ_OP_M) { --i; --j; } else if (ctype == FQ_OP_I) --j; else --i;
     ctype = type;
-    tb = trace[(size_t)j * W + i];
+    tb = get(j, i);
     type = type == FQ_OP_M ? (tb & 3) : type == FQ_OP_I ? ((tb & 4) ? FQ_OP_I : FQ_OP_M) : ((tb & 8) ? FQ_OP_D : FQ_OP_M);
     if (i || j) { ops[n++] = (uint8_t)ctype; li = i; lj = j; }
   } while (i || j);
   *n_ops = n;
   *fi = li; *fj = lj;
   return mx;
+}
+// The serial fill.  s1/s2 are 0-based code arrays; R holds len1+1 cells (single row, updated in place: the cell above is read
+// before it is overwritten, the diagonal one is carried in registers); trace = (len2+1)*(len1+1) bytes.
+template <class Rows>
+FQ_HD int fq_global_align(const uint8_t *s1, int len1, const uint8_t *s2, int len2, int band, int gap_end, const Rows &R,
+                          uint8_t *trace, uint8_t *ops, int *n_ops, int *fi, int *fj) {
+  if (len1 == 0 || len2 == 0) { *n_ops = 0; return 0; }
+  const FqBand g = fq_band(len1, len2, band, gap_end);
+  FqCell left;
+  left.M = 0; left.I = left.D = FQ_NEG_INF;
+  R.set(0, left);
+  uint8_t tb;
+  for (int i = 1; i < g.b1; ++i) { left = fq_band_row0(g, left, tb); trace[i] = tb; R.set(i, left); }
+  for (int j = 1; j <= len2; ++j) {
+    const FqBandRow r = fq_band_row(g, j);
+    const int c2 = s2[j - 1];
+    uint8_t *tr = trace + (size_t)j * (size_t)g.W;
+    FqCell diag = R.get(r.c0);
+    left = fq_band_left(g, r, diag, tb);
+    if (r.p15) tr[0] = tb;
+    R.set(r.c0, left);
+    for (int i = r.c0 + 1; i <= r.hi; ++i) {
+      const FqCell up = R.get(i);
+      left = fq_band_cell(g, r, i, diag, up, left, fq_sm_maq(s1[i - 1], c2), tb);
+      tr[i] = tb;
+      R.set(i, left);
+      diag = up;
+    }
+  }
+  return fq_traceback([&](int j, int i) { return trace[(size_t)j * g.W + i]; }, len1, len2, R.get(len1), ops, n_ops, fi, fj);
 }
 
 // path -> run-length cigar in alignment order (aln_path2cigar32 stdaln.c:1010-1040 + bwa_aln_path2cigar bwtaln.c:352)
@@ -2195,6 +2208,29 @@ FQ_HD FqDpScratch fq_dp_carve(uint8_t *base, int RL, int QL) {
   s.trace = p;
   return s;
 }
+
+// dynamic LDS of the wavefront DP kernels as byte offsets, walked once: the kernels carve by them, the launchers size by them
+FQ_HD size_t fq_pad16(size_t n) { return (n + 16) & ~(size_t)15; }
+struct FqSwLds {      // k_sw_wave: H, E, rows M/I/D, ref, qry, ops, and the trace matrix where the launcher found room for it
+  size_t H, E, rM, rI, rD, ref, qry, ops, trace, end;
+  FQ_HD FqSwLds(int RL, int QL) {
+    const size_t row = ((size_t)RL + 1) * sizeof(int);
+    H = 0; E = H + row + sizeof(int); rM = E + row + sizeof(int); rI = rM + row; rD = rI + row;
+    ref = rD + row; qry = ref + fq_pad16(RL); ops = qry + fq_pad16(QL); trace = ops + fq_pad16((size_t)RL + QL);
+    end = trace + ((size_t)RL + 1) * ((size_t)QL + 1) + 16;
+  }
+  FQ_HD size_t bytes(bool with_trace) const { return with_trace ? end : trace; }
+};
+struct FqRefineLds {  // k_refine_wave: rows M/I/D, ref, qry, ops, trace matrix of two cells per byte
+  size_t rM, rI, rD, ref, qry, ops, trace, end;
+  FQ_HD FqRefineLds(int RL, int QL) {
+    const size_t row = ((size_t)RL + 1) * sizeof(int);
+    rM = 0; rI = rM + row; rD = rI + row;
+    ref = rD + row; qry = ref + fq_pad16(RL); ops = qry + fq_pad16(QL); trace = ops + fq_pad16((size_t)RL + QL);
+    end = trace + (((size_t)RL + 2) >> 1) * ((size_t)QL + 1) + 16;
+  }
+  FQ_HD size_t bytes() const { return end; }
+};
 
 // ---- K_sw: bwa_sw_core (libbwa/bwape.c:359-445) with aln_local_core (stdaln.c:529-761) ----------
 // Scores stay far below the 32000 re-basing threshold of stdaln.c:247 for reads <= FQ_LMAX
@@ -2357,39 +2393,50 @@ FQ_HD void fq_sw_post(const FqSwTask &T, const uint8_t *ref, const uint8_t *qry,
   O.cnt = (uint32_t)n_mm << 16 | (uint32_t)n_gapo << 8 | (uint32_t)n_gape;
   O.n_cigar = n_cigar;
 }
+// the global fill of the sub-rectangle with a doubling band (stdaln.c:705-716); fill(s1, len1, s2, len2, band) returns the
+// score.  False: the "Potential bug" arm of the reference, ret < 0
+template <class Fill>
+FQ_HD bool fq_sw_band_fill(const uint8_t *ref, const uint8_t *qry, int score_f, int score_r, int start_i, int start_j, int end_i, int end_j, Fill fill) {
+  const int len1 = end_i - start_i + 1, len2 = end_j - start_j + 1, jmax = len1 > len2 ? len1 : len2;
+  int score_g;
+  for (int b = FQ_BAND;; b <<= 1) {
+    score_g = fill(ref + start_i - 1, len1, qry + start_j - 1, len2, b);
+    if (score_g == score_r || score_f == score_g) break;
+    if (b > jmax) break;
+  }
+  return !(score_r > score_g && score_f > score_g);
+}
 template <class Rows>
 FQ_HD void fq_sw_finish(const FqSwTask &T, const uint8_t *ref, int len1, const uint8_t *qry, int len, int score_f, int end_i, int end_j,
                         int *H, int *E, const Rows &R, uint8_t *trace, uint8_t *ops, uint16_t *cg, int cig_cap, FqSwOut &O) {
   if (score_f < 1) return;
   int start_i, start_j, score_r;
   fq_sw_reverse(ref, qry, score_f, end_i, end_j, H, E, &start_i, &start_j, &score_r);
-  int n_ops = 0, fi = 0, fj = 0, score_g;
-  const int jmax = (end_i - start_i > end_j - start_j ? end_i - start_i : end_j - start_j) + 1;
-  for (int b = FQ_BAND;; b <<= 1) {   // doubling band (stdaln.c:705-716)
-    score_g = fq_global_align(ref + start_i - 1, end_i - start_i + 1, qry + start_j - 1, end_j - start_j + 1, b, -1, R, trace, ops, &n_ops, &fi, &fj);
-    if (score_g == score_r || score_f == score_g) break;
-    if (b > jmax) break;
-  }
-  if (score_r > score_g && score_f > score_g) return;   // "Potential bug" arm of the reference: ret < 0
-  fq_sw_post(T, ref, qry, len, end_j, start_i, start_j, fi, fj, ops, n_ops, cg, cig_cap, O);
+  int n_ops = 0, fi = 0, fj = 0;
+  if (fq_sw_band_fill(ref, qry, score_f, score_r, start_i, start_j, end_i, end_j, [&](const uint8_t *s1, int l1, const uint8_t *s2, int l2, int b) {
+        return fq_global_align(s1, l1, s2, l2, b, -1, R, trace, ops, &n_ops, &fi, &fj); }))
+    fq_sw_post(T, ref, qry, len, end_j, start_i, start_j, fi, fj, ops, n_ops, cg, cig_cap, O);
 }
-FQ_HD bool fq_sw_prologue(const FqSwArgs &A, const FqSwTask &T, uint8_t *ref, uint8_t *qry, int *len_out, int *len1_out) {
+// bwa_sw_core's refusals (bwape.c:366-381); with nn = 0 it is the part that does not need the query
+FQ_HD bool fq_sw_refused(const FqSwTask &T, int len, int nn, int64_t l_pac) {
+  return T.reglen < 20 || l_pac - T.beg < len || (float)nn / len >= 0.25f || len - nn < 20;
+}
+// query and reference window, lane's share of n_lanes; returns the lane's count of N in the query
+FQ_HD int fq_sw_prologue(const FqSwArgs &A, const FqSwTask &T, uint8_t *ref, uint8_t *qry, int *len_out, int *len1_out, int lane, int n_lanes) {
   const int len = A.len_trim[T.read];
   const uint8_t *row = A.seq + (size_t)T.read * (size_t)A.stride;
-  const int64_t l_pac = A.ix.l_pac;
-  *len_out = len;
-  if (T.reglen < 20 || l_pac - T.beg < len) return false;
+  const int64_t avail = A.ix.l_pac - T.beg;
+  const int len1 = avail < (int64_t)T.reglen ? (avail > 0 ? (int)avail : 0) : T.reglen;
+  *len_out = len; *len1_out = len1;
+  if (fq_sw_refused(T, len, 0, A.ix.l_pac)) return 0;
   int nn = 0;
-  for (int k = 0; k < len; ++k) {
+  for (int k = lane; k < len; k += n_lanes) {
     const int c = T.use_rc ? fq_comp(fq_nt4(row[len - 1 - k])) : fq_nt4(row[k]);
     qry[k] = (uint8_t)c;
     nn += c >= 4;
   }
-  if ((float)nn / len >= 0.25f || len - nn < 20) return false;
-  int l1 = 0;
-  for (int64_t k = T.beg; l1 < T.reglen && k < l_pac; ++k) ref[l1++] = (uint8_t)fq_pac_base(A.ix.pac, k);
-  *len1_out = l1;
-  return true;
+  for (int k = lane; k < len1; k += n_lanes) ref[k] = (uint8_t)fq_pac_base(A.ix.pac, T.beg + k);
+  return nn;
 }
 
 // sequential form: one thread does the whole task (host-loop test backend; also the reference point for the wave kernel)
@@ -2399,7 +2446,8 @@ FQ_HD void fq_sw_thread(const FqSwArgs &A, int t) {
   O.beg = T.beg; O.cnt = 0; O.n_cigar = 0;
   FqDpScratch S = fq_dp_carve(A.scratch + (size_t)t * A.scratch_stride, A.RL, A.QL);
   int len, len1;
-  if (fq_sw_prologue(A, T, S.ref, S.qry, &len, &len1)) {
+  const int nn = fq_sw_prologue(A, T, S.ref, S.qry, &len, &len1, 0, 1);
+  if (!fq_sw_refused(T, len, nn, A.ix.l_pac)) {
     int score_f, end_i, end_j;
     fq_sw_forward_seq(S.ref, len1, S.qry, len, S.H, S.E, &score_f, &end_i, &end_j);
     FqRowsArr R = {S.rows};
@@ -2423,26 +2471,28 @@ struct FqRefineArgs {
   size_t scratch_stride;
   int32_t RL, QL;
 };
-template <class Rows>
-FQ_HD void fq_refine_task(const FqRefineArgs &A, int t, const Rows &R) {
-  const FqRefTask T = A.task[t];
-  const int len = A.len_trim[T.read];
-  const uint8_t *row = A.seq + (size_t)T.read * (size_t)A.stride;
+struct FqRefineWin { int64_t pos, k0; int len, l; };   // the sign-folded position, the window's first base, query and window lengths
+FQ_HD FqRefineWin fq_refine_window(const FqRefineArgs &A, const FqRefTask &T) {
   const int64_t l_pac = A.ix.l_pac;
-  FqDpScratch S = fq_dp_carve(A.scratch + (size_t)t * A.scratch_stride, A.RL, A.QL);
-  for (int k = 0; k < len; ++k) S.qry[k] = (uint8_t)(T.strand ? fq_comp(fq_nt4(row[len - 1 - k])) : fq_nt4(row[k]));
-  int64_t pos = (int64_t)T.pos > l_pac ? (int64_t)(int32_t)T.pos : (int64_t)T.pos;
-  const int aext = T.ext < 0 ? -T.ext : T.ext, ref_len = len + aext;
-  int l = 0;
-  if (T.ext > 0) { for (int64_t k = pos; k < pos + ref_len && k < l_pac; ++k) S.ref[l++] = (uint8_t)fq_pac_base(A.ix.pac, k); }
-  else {
-    const int64_t x = pos + len;
-    for (int64_t k = x - ref_len > 0 ? x - ref_len : 0; k < x && k < l_pac; ++k) S.ref[l++] = (uint8_t)fq_pac_base(A.ix.pac, k);
-  }
-  int n_ops = 0, fi, fj;
-  fq_global_align(S.ref, l, S.qry, len, FQ_BAND, FQ_GAP_END, R, S.trace, S.ops, &n_ops, &fi, &fj);
+  FqRefineWin w;
+  w.len = A.len_trim[T.read];
+  w.pos = (int64_t)T.pos > l_pac ? (int64_t)(int32_t)T.pos : (int64_t)T.pos;
+  const int aext = T.ext < 0 ? -T.ext : T.ext, ref_len = w.len + aext;
+  int64_t k1;
+  if (T.ext > 0) { w.k0 = w.pos; k1 = w.pos + ref_len < l_pac ? w.pos + ref_len : l_pac; }
+  else { const int64_t x = w.pos + w.len; w.k0 = x - ref_len > 0 ? x - ref_len : 0; k1 = x < l_pac ? x : l_pac; }
+  w.l = k1 > w.k0 ? (int)(k1 - w.k0) : 0;
+  return w;
+}
+FQ_HD void fq_refine_fetch(const FqRefineArgs &A, const FqRefTask &T, const FqRefineWin &w, uint8_t *qry, uint8_t *ref, int lane, int n_lanes) {
+  const uint8_t *row = A.seq + (size_t)T.read * (size_t)A.stride;
+  for (int k = lane; k < w.len; k += n_lanes) qry[k] = (uint8_t)(T.strand ? fq_comp(fq_nt4(row[w.len - 1 - k])) : fq_nt4(row[k]));
+  for (int k = lane; k < w.l; k += n_lanes) ref[k] = (uint8_t)fq_pac_base(A.ix.pac, w.k0 + k);
+}
+// the path as the task's CIGAR: position shift of a backward extension, leading / trailing D dropped, I at either end -> S
+FQ_HD void fq_refine_emit(const FqRefineArgs &A, int t, const FqRefTask &T, int64_t pos, const uint8_t *ops, int n_ops) {
   uint16_t *cg = A.cigar + (size_t)t * (size_t)A.cig_cap;
-  int n = fq_ops_to_cigar(S.ops, n_ops, cg, A.cig_cap);
+  int n = fq_ops_to_cigar(ops, n_ops, cg, A.cig_cap);
   FqRefOut O;
   if (n <= 0) { O.pos = T.pos; O.n_cigar = 0; A.out[t] = O; return; }
   if (T.ext < 0) {
@@ -2456,6 +2506,16 @@ FQ_HD void fq_refine_task(const FqRefineArgs &A, int t, const Rows &R) {
   if ((cg[0] >> 14) == FQ_OP_I) cg[0] = (uint16_t)(FQ_OP_S << 14 | (cg[0] & 0x3fff));
   O.pos = (uint32_t)pos; O.n_cigar = n;
   A.out[t] = O;
+}
+template <class Rows>
+FQ_HD void fq_refine_task(const FqRefineArgs &A, int t, const Rows &R) {
+  const FqRefTask T = A.task[t];
+  const FqDpScratch S = fq_dp_carve(A.scratch + (size_t)t * A.scratch_stride, A.RL, A.QL);
+  const FqRefineWin w = fq_refine_window(A, T);
+  fq_refine_fetch(A, T, w, S.qry, S.ref, 0, 1);
+  int n_ops = 0, fi, fj;
+  fq_global_align(S.ref, w.l, S.qry, w.len, FQ_BAND, FQ_GAP_END, R, S.trace, S.ops, &n_ops, &fi, &fj);
+  fq_refine_emit(A, t, T, w.pos, S.ops, n_ops);
 }
 FQ_HD void fq_refine_thread(const FqRefineArgs &A, int t) {
   FqDpScratch S = fq_dp_carve(A.scratch + (size_t)t * A.scratch_stride, A.RL, A.QL);
