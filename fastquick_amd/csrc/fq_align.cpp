@@ -341,6 +341,12 @@ struct fq_ctx {
   bool host_rows = true;               // the last text batch's surviving rows were copied to the host
   DevBuf<uint8_t> d_equal; PinBuf<uint8_t> p_equal;
   DevBuf<char> d_enames; PinBuf<char> p_enames;
+  int e_qstride = 0, e_nstride = 0;    // the strides of p_equal / p_enames (0: not gathered for the last call, gather_reads)
+  // the last call as the host formatters read it (fq_ctx_host_view): made when the first of them asks, valid until the next call
+  std::mutex view_mu;
+  bool view_ready = false;
+  FqSamArgs view{};
+  vector<uint8_t> h_eseq;              // ... the surviving reads' bases of a packed batch as letters, compact like p_equal
   DevBuf<uint32_t> d_samlen, d_sammeta; DevBuf<uint64_t> d_samoff; DevBuf<char> d_samtext;
   uint64_t sam_bytes = 0;
   bool sam_ready = false;
@@ -665,6 +671,7 @@ inline int default_host_threads(const fq_index *ix) {
   const unsigned share = 2 * hw / (unsigned)std::max(1, g_calls_in_flight.load(std::memory_order_relaxed));   // (a call waits for the device about half of its time)
   return (int)std::max(std::min(2u, cap), std::min(cap, share));
 }
+inline int call_host_threads(const fq_ctx *c) { return c->kn.host_threads >= 0 ? c->kn.host_threads : c->o.host_threads > 0 ? c->o.host_threads : default_host_threads(c->ix); }
 // The calling thread of a call hands its passes to the context's worker pool (run_call sets tl_pool); the side threads a call
 // starts (record set-up, the drand48 plan) have none and fork their own helpers, so that they never queue behind the main thread's.
 static thread_local FqWorkPool *tl_pool = nullptr;
@@ -2040,18 +2047,17 @@ int snapshot_records(Call &K, vector<FqRead> &dst) {
 
 // ---- the consumers on the device (fq_emit.h): the SAM text of the call, formatted from the result arrays where they lie ----------------
 // The reads' qualities and names are resident for a text batch (fq_align_text); for ASCII and packed batches the surviving reads' are gathered
-// on the host and uploaded compact (row = 2 * survivor + end).
-int emit_reads(Call &K, const uint8_t **qual, int *qual_stride, const char **names, int *name_stride) {
-  fq_ctx *c = K.c;
-  const size_t N = (size_t)K.n_surv * 2;
-  if (c->in_kind == 3) { *qual = c->d_pqual.p; *qual_stride = c->c_stride; *names = c->d_cnames.p; *name_stride = c->c_name_stride; return FQ_OK; }
+// on the host, compact (row = 2 * survivor + end), once per call: the consumers' kernels read an upload of them (emit_reads), the host
+// formatters the rows themselves (fq_ctx_host_view).
+int gather_reads(fq_ctx *c, int threads, size_t par_min) {
+  if (c->e_qstride) return FQ_OK;
+  const size_t N = (size_t)c->st.n_surv * 2;
   const FqHostReads hb = fq_ctx_host_reads(c);
-  if (N && !hb.has_qual()) { c->err = "SAM text on the device: the batch carries no qualities"; return FQ_EINVAL; }
-  const int n = K.n;
+  const int n = c->n_pairs;
   const bool se = c->o.single_end != 0;
   int max_len = 1, max_name = 1;
-  std::vector<int> tl((size_t)std::max(1, K.host_threads), 1), tn((size_t)std::max(1, K.host_threads), 1);
-  parallel_chunks(N, K.host_threads, K.par_min, [&](size_t lo, size_t hi, int t) {
+  std::vector<int> tl((size_t)std::max(1, threads), 1), tn((size_t)std::max(1, threads), 1);
+  parallel_chunks(N, threads, par_min, [&](size_t lo, size_t hi, int t) {
     int ml = 1, mn = 1;
     for (size_t i = lo; i < hi; ++i) {
       const int e = (int)(i & 1), pair = c->h_pair_list[i >> 1];
@@ -2063,8 +2069,8 @@ int emit_reads(Call &K, const uint8_t **qual, int *qual_stride, const char **nam
   });
   for (size_t t = 0; t < tl.size(); ++t) { max_len = std::max(max_len, tl[t]); max_name = std::max(max_name, tn[t]); }
   const int qs = (max_len + 15) & ~15, ns = (max_name + 1 + 7) & ~7;
-  CKM(c->p_equal.ensure(N * qs + 64) && c->d_equal.ensure(N * qs + 64) && c->p_enames.ensure(N * ns + 64) && c->d_enames.ensure(N * ns + 64));
-  parallel_chunks(N, K.host_threads, K.par_min, [&](size_t lo, size_t hi, int) {
+  CKM(c->p_equal.ensure(N * qs + 64) && c->p_enames.ensure(N * ns + 64));
+  parallel_chunks(N, threads, par_min, [&](size_t lo, size_t hi, int) {
     for (size_t i = lo; i < hi; ++i) {
       const int e = (int)(i & 1), pair = c->h_pair_list[i >> 1];
       uint8_t *q = c->p_equal.p + i * (size_t)qs;
@@ -2079,10 +2085,21 @@ int emit_reads(Call &K, const uint8_t **qual, int *qual_stride, const char **nam
       else nm[0] = '*';
     }
   });
+  c->e_qstride = qs; c->e_nstride = ns;
+  return FQ_OK;
+}
+int emit_reads(Call &K, const uint8_t **qual, int *qual_stride, const char **names, int *name_stride) {
+  fq_ctx *c = K.c;
+  const size_t N = (size_t)K.n_surv * 2;
+  if (c->in_kind == 3) { *qual = c->d_pqual.p; *qual_stride = c->c_stride; *names = c->d_cnames.p; *name_stride = c->c_name_stride; return FQ_OK; }
+  if (N && !fq_ctx_host_reads(c).has_qual()) { c->err = "SAM text on the device: the batch carries no qualities"; return FQ_EINVAL; }
+  CKS(gather_reads(c, K.host_threads, K.par_min));
+  const size_t qs = (size_t)c->e_qstride, ns = (size_t)c->e_nstride;
+  CKM(c->d_equal.ensure(N * qs + 64) && c->d_enames.ensure(N * ns + 64));
   CK(fqdev::copy_pinned(c->d_equal.p, c->p_equal.p, N * qs, 1));
   CK(fqdev::copy_pinned(c->d_enames.p, c->p_enames.p, N * ns, 1));
-  c->stats.h2d_bytes += N * ((size_t)qs + (size_t)ns);
-  *qual = c->d_equal.p; *qual_stride = qs; *names = c->d_enames.p; *name_stride = ns;
+  c->stats.h2d_bytes += N * (qs + ns);
+  *qual = c->d_equal.p; *qual_stride = (int)qs; *names = c->d_enames.p; *name_stride = (int)ns;
   return FQ_OK;
 }
 // the call's records, reads and names as the consumers' kernels see them (qualities and names uploaded once per call)
@@ -2375,6 +2392,7 @@ int run_call_stages(fq_ctx *c, fq_result_batch_t *out) {
   FqBatchState &S = c->st;
   S.clear();
   S.n_pairs = c->n_pairs;
+  c->e_qstride = c->e_nstride = 0; c->view_ready = false;
   memset(out, 0, sizeof *out);
   out->n_pairs = c->n_pairs;
   if (c->n_pairs == 0) {
@@ -2384,7 +2402,7 @@ int run_call_stages(fq_ctx *c, fq_result_batch_t *out) {
   }
   K.n = c->n_pairs; K.n2 = 2 * K.n; K.B = o.batch_pairs; K.n_sub = (K.n + K.B - 1) / K.B;
   K.par_min = c->kn.host_par_min;
-  K.host_threads = c->kn.host_threads >= 0 ? c->kn.host_threads : o.host_threads > 0 ? o.host_threads : default_host_threads(c->ix);
+  K.host_threads = call_host_threads(c);
   int rc = c->in_kind == 3 ? stage0_text(K) : c->in_kind == 2 ? stage0_packed(K) : stage0_ascii(K);
   if (rc) return rc;
   S.n_surv = K.n_surv;
@@ -2746,6 +2764,50 @@ FqHostReads fq_ctx_host_reads(const fq_ctx_t *c) {
   } else if (c->in_kind == 2) { h.p = &c->pb; h.n_pairs = c->pb.n_pairs; h.names = c->pb.names; h.names_mate = c->pb.names_mate; h.name_stride = c->pb.name_stride; }
   else { h.a = &c->hb; h.n_pairs = c->hb.n_pairs; h.names = c->hb.names; h.names_mate = c->hb.names_mate; h.name_stride = c->hb.name_stride; }
   return h;
+}
+// The last call as fq_emit.h's routines read it, every pointer in HOST memory (len / off / meta / text are the formatter's own): the result
+// arrays where they landed, the qualities and names compact as the consumers' kernels get them, the bases where the input kind leaves them --
+// the caller's rows of an ASCII batch, a text batch's compact rows, the surviving rows of a packed batch decoded to letters.
+int fq_ctx_host_view(fq_ctx_t *c, FqSamArgs *a) {
+  std::lock_guard<std::mutex> lk(c->view_mu);
+  if (!c->view_ready) {
+    const FqBatchState &S = c->st;
+    const FqHostReads hb = fq_ctx_host_reads(c);
+    if (S.n_surv > 0 && !S.rec) { c->err = "the call's result arrays were left on the device (FQ_EMIT_DEVICE_ONLY)"; return FQ_EINVAL; }
+    if (S.n_surv > 0 && !hb.has_qual()) { c->err = "the batch carries no qualities"; return FQ_EINVAL; }
+    FqSamArgs &e = c->view;
+    e = FqSamArgs{};
+    e.cg = c->ix->host_contigs;
+    e.n_surv = S.n_surv; e.n_pairs = S.n_pairs; e.packed = 1; e.single_end = c->o.single_end; e.mode = c->o.mode; e.max_top2 = c->o.max_top2;
+    e.pair_list = S.pair_idx;
+    e.rec = S.rec; e.cigar = S.cigar; e.md = S.md; e.multi = S.multi;
+    if (c->in_kind == 3) {
+      e.seq = c->p_cseq.p; e.stride = c->c_stride;
+      e.qual = c->p_cqual.p; e.qual_stride = c->c_stride; e.names = c->p_cnames.p; e.name_stride = c->c_name_stride;
+    } else {
+      const int threads = call_host_threads(c);
+      CKS(gather_reads(c, threads, c->kn.host_par_min));
+      const size_t N = (size_t)S.n_surv * 2, qs = (size_t)c->e_qstride;
+      e.qual = c->p_equal.p; e.qual_stride = c->e_qstride; e.names = c->p_enames.p; e.name_stride = c->e_nstride;
+      if (c->in_kind == 2) {   // rows as fq_unpack_thread / fq_patch_thread leave them on the device
+        c->h_eseq.resize(N * qs + 64);
+        parallel_chunks(N, threads, c->kn.host_par_min, [&](size_t lo, size_t hi, int) {
+          for (size_t i = lo; i < hi; ++i) {
+            uint8_t *row = c->h_eseq.data() + i * qs;
+            const size_t r = (i & 1) * (size_t)S.n_pairs + (size_t)S.pair_idx[i >> 1];
+            const int l = (c->o.single_end && (i & 1)) ? 0 : hb.len(r);
+            hb.codes(r, l, row);
+            for (int j = 0; j < l; ++j) row[j] = (uint8_t)(row[j] < 4 ? "ACGT"[row[j]] : row[j] == 5 ? '-' : 'N');
+            memset(row + l, 0, qs - (size_t)l);
+          }
+        });
+        e.seq = c->h_eseq.data(); e.stride = c->e_qstride;
+      } else { e.seq = c->hb.seq; e.stride = c->hb.stride; e.packed = 0; }
+    }
+    c->view_ready = true;
+  }
+  *a = c->view;
+  return FQ_OK;
 }
 const fq_opts_t *fq_ctx_opts(const fq_ctx_t *c) { return &c->o; }
 int64_t fq_ctx_last_bases(const fq_ctx_t *c) { return c->n_bases_in; }

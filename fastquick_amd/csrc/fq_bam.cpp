@@ -2,8 +2,8 @@
 // branches that are compiled in: :946) and SetSamFileHeader (:947-975), written as BAM through an own BGZF layer (zlib raw deflate
 // in 64 KB blocks).  Unlike the --sam_out dialect the records carry GENOME coordinates: a reduced-reference contig is named
 // CHR:POS@REF/ALT[|L], the record's RNAME is CHR and its position POS - flank + offset-in-contig - 1 (:1026-1043), the header's
-// @SQ lines are the original reference's (.fai), and every record carries RG:Z.  Records are built after StatCollector's
-// contig-end un-mapping (AddAlignment runs first, :2075-2079).
+// @SQ lines are the original reference's (.fai), and every record carries RG:Z.  The record itself is fq_emit.h's fq_bam_record, the
+// routine the consumers' kernels run: the host formatter loops over it on the host's view of the call (fq_ctx_host_view).
 #include <zlib.h>
 
 #include <cstdio>
@@ -99,73 +99,12 @@ struct Bgzf {
   }
 };
 
-int64_t ref_end(const FqRead &p) {   // pos_end, libbwa/bwase.c:420-432
-  if (!p.cigar.empty()) { int64_t x = p.pos; for (uint16_t g : p.cigar) { const int op = g >> 14; if (op == FQ_OP_M || op == FQ_OP_D) x += g & 0x3fff; } return x; }
-  return (int64_t)p.pos + p.len;
-}
-int64_t ref_end_multi(const FqMulti &q, int len) {
-  if (!q.cigar.empty()) { int64_t x = q.pos; for (uint16_t g : q.cigar) { const int op = g >> 14; if (op == FQ_OP_M || op == FQ_OP_D) x += g & 0x3fff; } return x; }
-  return (int64_t)q.pos + len;
-}
-int64_t five_prime(const FqRead &p) { return p.type != FQ_TYPE_NO_MATCH ? (p.strand ? ref_end(p) : (int64_t)p.pos) : -1; }
-int reg2bin(int64_t beg, int64_t end) {   // SAM specification 5.3
-  --end;
-  if (beg >> 14 == end >> 14) return (int)(((1 << 15) - 1) / 7 + (beg >> 14));
-  if (beg >> 17 == end >> 17) return (int)(((1 << 12) - 1) / 7 + (beg >> 17));
-  if (beg >> 20 == end >> 20) return (int)(((1 << 9) - 1) / 7 + (beg >> 20));
-  if (beg >> 23 == end >> 23) return (int)(((1 << 6) - 1) / 7 + (beg >> 23));
-  if (beg >> 26 == end >> 26) return (int)(((1 << 3) - 1) / 7 + (beg >> 26));
-  return 0;
-}
-// The optional fields of a record.  The reference keeps them in SamRecord's hash of tags (LongHash<int> extras, 32 slots, slot =
-// key & mask with linear probing, key = type << 16 | tag[1] << 8 | tag[0]: misc/bam/SamRecord.h:629, VerifyBamID/statgen/LongHash.h)
-// and writes them to the record in slot order (setTagsInBuffer, misc/bam/SamRecord.cpp:3308-3340), not in the order SetSamRecord
-// adds them: AM MD NM RG SM, then the X? tags in the order they were added.  bytes() replays the insertions and walks the slots.
-struct Tags {
-  struct Entry { uint8_t t0, t1; std::vector<uint8_t> b; };
-  std::vector<Entry> list;           // in the order SetSamRecord adds them
-  std::vector<uint8_t> *cur = nullptr;
-  void key(const char *t, char type) {
-    list.push_back(Entry{(uint8_t)t[0], (uint8_t)t[1], {}});
-    cur = &list.back().b;
-    cur->push_back((uint8_t)t[0]); cur->push_back((uint8_t)t[1]); cur->push_back((uint8_t)type);
-  }
-  void z(const char *t, const std::string &v) { key(t, 'Z'); cur->insert(cur->end(), v.begin(), v.end()); cur->push_back(0); }
-  void a(const char *t, char v) { key(t, 'A'); cur->push_back((uint8_t)v); }
-  void i(const char *t, long long v) {   // smallest integer type that holds the value
-    if (v >= 0 && v <= 255) { key(t, 'C'); cur->push_back((uint8_t)v); }
-    else if (v >= -128 && v <= 127) { key(t, 'c'); cur->push_back((uint8_t)(int8_t)v); }
-    else if (v >= 0 && v <= 65535) { key(t, 'S'); const uint16_t x = (uint16_t)v; cur->insert(cur->end(), (const uint8_t *)&x, (const uint8_t *)&x + 2); }
-    else if (v >= -32768 && v <= 32767) { key(t, 's'); const int16_t x = (int16_t)v; cur->insert(cur->end(), (const uint8_t *)&x, (const uint8_t *)&x + 2); }
-    else { key(t, 'i'); const int32_t x = (int32_t)v; cur->insert(cur->end(), (const uint8_t *)&x, (const uint8_t *)&x + 4); }
-  }
-  std::vector<uint8_t> bytes() const {
-    std::vector<int> slot(32, -1);
-    auto place = [&](std::vector<int> &tab, int e) {
-      const size_t mask = tab.size() - 1;
-      size_t h = list[(size_t)e].t0 & mask;      // (the table never outgrows 256 slots here: the key's low byte is the tag's first letter)
-      while (tab[h] >= 0) h = (h + 1) & mask;
-      tab[h] = e;
-    };
-    size_t count = 0;
-    for (size_t e = 0; e < list.size(); ++e) {
-      if (count * 2 > slot.size()) {               // LongHash::Add grows before it inserts; SetSize re-inserts in slot order
-        std::vector<int> bigger(slot.size() * 2, -1);
-        for (int old : slot) if (old >= 0) place(bigger, old);
-        slot.swap(bigger);
-      }
-      place(slot, (int)e);
-      ++count;
-    }
-    std::vector<uint8_t> out;
-    for (int e : slot) if (e >= 0) out.insert(out.end(), list[(size_t)e].b.begin(), list[(size_t)e].b.end());
-    return out;
-  }
-};
 }  // namespace
 
 struct fq_bam {
-  // the formatter's tables on the device (fq_emit.h): per contig the BAM reference id of its chromosome and where it lies in the genome
+  // the formatter's tables (fq_emit.h: FqBamArgs): per contig the BAM reference id of its chromosome and where it lies in the genome;
+  // made with the writer, uploaded when the first call formats on the device
+  std::vector<int32_t> ctg_rid, ctg_g0;
   std::mutex dev_mu;
   bool dev_on = false;
   bool host_deflate = [] { const char *e = getenv("FASTQUICK_BAM_HOST_DEFLATE"); return e && *e && *e != '0'; }();   // A/B: zlib on the host's threads for device-formatted records too
@@ -176,7 +115,7 @@ struct fq_bam {
   const fq_index *ix = nullptr;
   fq_qc_opts_t o{};
   Bgzf z;
-  std::vector<uint8_t> last;                             // fq_bam_format_last: the records of the last batch it formatted
+  std::vector<uint8_t> last;                             // the records of the last batch the host formatter made, or fq_bam_format_last fetched
   std::string err, rg_id, header_text;
   std::vector<std::pair<std::string, int>> contigs;      // BwtIndexer::contigSize
   std::map<std::string, int> ref_id;
@@ -190,117 +129,7 @@ struct fq_bam {
     *start = refCoord - (name.back() == 'L' ? o.flank_long_len : o.flank_len) + pos1 - 1;
   }
   int id_of(const std::string &chrom) const { auto it = ref_id.find(chrom); return it == ref_id.end() ? -1 : it->second; }
-  // appends one BAM record to `dst`; se: SetSamRecord(p, mate = 0)
-  void record(std::vector<uint8_t> &dst, const fq_opts_t *ao, const FqHostReads &hb, int n_pairs, FqRead p, const FqRead &mate, bool se = false) const;
 };
-
-// SetSamRecord, src/BwtMapper.cpp:977-1264
-void fq_bam::record(std::vector<uint8_t> &dst, const fq_opts_t *ao, const FqHostReads &hb, int n_pairs, FqRead p, const FqRead &mate, bool se) const {
-  const std::string name = fq_read_name(&hb, p.r % n_pairs, p.r / n_pairs, p.revived);
-  uint8_t codes[FQ_LMAX + 8];
-  hb.codes((size_t)p.r, p.full_len, codes);
-  const uint8_t *hq = hb.qual((size_t)p.r);
-  const int qsub = (ao->mode & FQ_MODE_IL13) ? 31 : 0;
-  int flag, rid = -1, pos1 = 0, mrid = -1, mpos1 = 0, mapq = 0;
-  long long isize = 0;
-  std::vector<uint16_t> cigar;
-  std::string seq, qual;
-  Tags T;
-  bool mate_same = false;
-  if (p.type != FQ_TYPE_NO_MATCH || (!se && mate.type != FQ_TYPE_NO_MATCH)) {
-    int seqid, nn, am = 0, j, readRealStart = 0;
-    flag = p.extra_flag;
-    if (p.type == FQ_TYPE_NO_MATCH) { p.pos = mate.pos; p.strand = mate.strand; flag |= 4; j = 1; }
-    else j = (int)(ref_end(p) - p.pos);
-    nn = fq_coor_pac2real(ix, p.pos, j, &seqid);
-    if (p.type != FQ_TYPE_NO_MATCH && (int64_t)p.pos + j - ix->contigs[seqid].offset > ix->contigs[seqid].len) flag |= 4;
-    if (p.strand) flag |= 16;
-    if (!se) { if (mate.type != FQ_TYPE_NO_MATCH) { if (mate.strand) flag |= 32; } else flag |= 8; }
-    std::string chrom;
-    if (p.type == FQ_TYPE_NO_MATCH) { rid = -1; pos1 = 0; }
-    else { genome_coord(seqid, (int)((int64_t)p.pos - ix->contigs[seqid].offset + 1), &chrom, &readRealStart); rid = id_of(chrom); pos1 = readRealStart; }
-    mapq = p.mapQ;
-    if (p.type != FQ_TYPE_NO_MATCH) { if (!p.cigar.empty()) cigar = p.cigar; else cigar.push_back((uint16_t)(FQ_OP_M << 14 | p.len)); }
-    if (se) { mrid = -1; mpos1 = 0; isize = 0; }      // no mate: "*", 0, 0 (:1118-1122)
-    else if (mate.type != FQ_TYPE_NO_MATCH) {
-      int m_seqid, mstart;
-      am = mate.seQ < p.seQ ? mate.seQ : p.seQ;
-      fq_coor_pac2real(ix, mate.pos, mate.len, &m_seqid);
-      std::string mchrom;
-      genome_coord(m_seqid, (int)((int64_t)mate.pos - ix->contigs[m_seqid].offset + 1), &mchrom, &mstart);
-      mate_same = seqid == m_seqid;
-      mrid = mate_same ? rid : id_of(mchrom);     // "=" is resolved against this record's own reference
-      isize = mate_same ? five_prime(mate) - five_prime(p) : 0;
-      if (p.type == FQ_TYPE_NO_MATCH) isize = 0;
-      mpos1 = mstart;
-    } else { mate_same = true; mrid = rid; mpos1 = readRealStart; isize = 0; }
-    if (p.strand == 0) for (j = 0; j != p.full_len; ++j) seq += "ACGTN"[codes[j] > 4 ? 4 : codes[j]];
-    else for (j = 0; j != p.full_len; ++j) { const int c = codes[p.full_len - 1 - j]; seq += "TGCAN"[c > 4 ? 4 : c]; }
-    // qualities: 31 back on the first len bytes of Phred+64 input, the first len bytes reversed for a reverse-strand record
-    for (j = 0; j < p.full_len; ++j) {
-      const int src = (p.strand && j < p.len) ? p.len - 1 - j : j;
-      qual += (char)(j < p.len ? hq[src] : hq[src] - qsub);
-    }
-    if (!rg_id.empty()) T.z("RG", rg_id);
-    if (p.clip_len < p.full_len) T.i("XC", p.clip_len);
-    if (p.type != FQ_TYPE_NO_MATCH) {
-      char XT = "NURM"[p.type];
-      if (nn > 10) XT = 'N';
-      T.a("XT", XT);
-      T.i((ao->mode & FQ_MODE_COMPREAD) ? "NM" : "CM", p.nm);
-      if (nn) T.i("XN", nn);
-      if (!se) { T.i("SM", p.seQ); T.i("AM", am); }
-      if (p.type != FQ_TYPE_MATESW) { T.i("X0", p.c1); if ((int)p.c1 <= ao->max_top2) T.i("X1", p.c2); }
-      T.i("XM", p.n_mm); T.i("XO", p.n_gapo); T.i("XG", p.n_gapo + p.n_gape);
-      if (p.has_md) T.z("MD", p.md);
-      if (!p.multi.empty()) {
-        std::ostringstream ss;
-        for (const FqMulti &q : p.multi) {
-          int sid;
-          fq_coor_pac2real(ix, q.pos, (int)(ref_end_multi(q, p.len) - q.pos), &sid);
-          ss << ix->contigs[sid].name << "," << (q.strand ? '-' : '+') << (int)((int64_t)q.pos - ix->contigs[sid].offset + 1) << ",";
-          if (!q.cigar.empty()) for (uint16_t g : q.cigar) ss << (g & 0x3fff) << "MIDS"[g >> 14]; else ss << p.len << "M";
-          ss << "," << q.gap + q.mm << ";";
-        }
-        T.z("XA", ss.str());
-      }
-    }
-  } else {   // no match on either mate (:1225-1257)
-    flag = p.extra_flag | 4 | (se ? 0 : 8);
-    for (int j = 0; j != p.len; ++j) {
-      int cc = codes[j];
-      if (p.strand) { cc = j < p.clip_len ? codes[p.clip_len - 1 - j] : 3; cc = cc < 4 ? 3 - cc : cc; }
-      seq += "ACGTN"[cc > 4 ? 4 : cc];
-    }
-    for (int j = 0; j < p.full_len; ++j) qual += (char)(hq[(p.strand && j < p.len) ? p.len - 1 - j : j] - qsub);
-    if (!rg_id.empty()) T.z("RG", rg_id);
-    if (p.clip_len < p.full_len) T.i("XC", p.clip_len);
-  }
-  // ---- BAM record (SAM specification 4.2) ----
-  int64_t end0 = pos1 > 0 ? pos1 - 1 : 0;
-  for (uint16_t g : cigar) { const int op = g >> 14; if (op == FQ_OP_M || op == FQ_OP_D) end0 += g & 0x3fff; }
-  const int bin = pos1 > 0 ? reg2bin(pos1 - 1, cigar.empty() ? pos1 : end0) : 4680;
-  std::vector<uint8_t> rec;
-  auto put32 = [&](int32_t v) { rec.insert(rec.end(), (const uint8_t *)&v, (const uint8_t *)&v + 4); };
-  auto put16 = [&](uint16_t v) { rec.insert(rec.end(), (const uint8_t *)&v, (const uint8_t *)&v + 2); };
-  put32(rid); put32(pos1 - 1);
-  rec.push_back((uint8_t)(name.size() + 1)); rec.push_back((uint8_t)mapq); put16((uint16_t)bin);
-  put16((uint16_t)cigar.size()); put16((uint16_t)flag); put32((int32_t)seq.size());
-  put32(mrid); put32(mpos1 - 1); put32((int32_t)isize);
-  rec.insert(rec.end(), name.begin(), name.end()); rec.push_back(0);
-  static const int bam_op[4] = {0, 1, 2, 4};   // M I D S
-  for (uint16_t g : cigar) put32((int32_t)((uint32_t)(g & 0x3fff) << 4 | (uint32_t)bam_op[g >> 14]));
-  for (size_t j = 0; j < seq.size(); j += 2) {
-    auto nib = [](char c) { return c == 'A' ? 1 : c == 'C' ? 2 : c == 'G' ? 4 : c == 'T' ? 8 : 15; };
-    rec.push_back((uint8_t)(nib(seq[j]) << 4 | (j + 1 < seq.size() ? nib(seq[j + 1]) : 0)));
-  }
-  for (size_t j = 0; j < seq.size(); ++j) rec.push_back((uint8_t)(j < qual.size() ? qual[j] - 33 : 0xff));
-  { const std::vector<uint8_t> tb = T.bytes(); rec.insert(rec.end(), tb.begin(), tb.end()); }
-  const int32_t bs = (int32_t)rec.size();
-  dst.insert(dst.end(), (const uint8_t *)&bs, (const uint8_t *)&bs + 4);
-  dst.insert(dst.end(), rec.begin(), rec.end());
-  (void)mate_same;
-}
 
 extern "C" int fq_bam_create(const fq_index_t *ix, const char *fai_path, const char *bam_path, const char *rg_line, const fq_qc_opts_t *o, fq_bam_t **out) {
   if (!ix || !fai_path || !o || !out) return FQ_EINVAL;
@@ -341,6 +170,12 @@ extern "C" int fq_bam_create(const fq_index_t *ix, const char *fai_path, const c
     b->ref_id.emplace(b->contigs[i].first, (int)i);   // (a repeated name keeps its first id)
   }
   b->header_text = h.str();
+  for (size_t i = 0; i < ix->contigs.size(); ++i) {
+    std::string chrom; int start;
+    b->genome_coord((int)i, 1, &chrom, &start);        // start = refCoord - flank + 1 - 1
+    b->ctg_rid.push_back(b->id_of(chrom)); b->ctg_g0.push_back(start);
+  }
+  b->ctg_rid.push_back(-1); b->ctg_g0.push_back(0);      // (one entry behind the last contig, as the tables always had)
   if (!bam_path) { *out = b; return FQ_OK; }          // a formatter without a file (fq_bam_format_last)
   b->z.fp = fopen(bam_path, "wb");
   if (!b->z.fp) { delete b; return FQ_EIO; }
@@ -364,13 +199,6 @@ bool fq_bam_wants_members(const fq_bam *b) { return b->z.fp != nullptr && !b->ho
 int fq_bam_device_prepare(fq_bam *b, FqBamArgs *a) {
   std::lock_guard<std::mutex> lk(b->dev_mu);
   if (!b->dev_on) {
-    const size_t nc = b->ix->contigs.size();
-    std::vector<int32_t> rid(nc + 1, -1), g0(nc + 1, 0);
-    for (size_t i = 0; i < nc; ++i) {
-      std::string chrom; int start;
-      b->genome_coord((int)i, 1, &chrom, &start);        // start = refCoord - flank + 1 - 1
-      rid[i] = b->id_of(chrom); g0[i] = start;
-    }
     bool ok = true;
     auto up = [&](const void *src, size_t bytes) -> void * {
       void *d = fqdev::dmalloc(bytes ? bytes : 16);
@@ -379,7 +207,7 @@ int fq_bam_device_prepare(fq_bam *b, FqBamArgs *a) {
       if (bytes && fqdev::h2d(d, src, bytes)) ok = false;
       return d;
     };
-    b->d_rid = (const int32_t *)up(rid.data(), rid.size() * 4); b->d_g0 = (const int32_t *)up(g0.data(), g0.size() * 4);
+    b->d_rid = (const int32_t *)up(b->ctg_rid.data(), b->ctg_rid.size() * 4); b->d_g0 = (const int32_t *)up(b->ctg_g0.data(), b->ctg_g0.size() * 4);
     b->d_rg = (const char *)up(b->rg_id.c_str(), b->rg_id.size() + 1);
     if (!ok || fqdev::sync()) return FQ_ENODEV;
     b->dev_on = true;
@@ -388,48 +216,21 @@ int fq_bam_device_prepare(fq_bam *b, FqBamArgs *a) {
   return FQ_OK;
 }
 
-// the BAM branch of PairEndMapper's consumer loop over one batch (src/BwtMapper.cpp:2054-2085): the batch's records, in input order
-static int format_last(fq_bam_t *b, fq_ctx_t *c, std::vector<std::vector<uint8_t>> &parts) {
-  const FqBatchState *S = fq_ctx_state(c);
-  const FqHostReads hb = fq_ctx_host_reads(c);
-  const fq_opts_t *ao = fq_ctx_opts(c);
-  if (S->n_surv > 0 && !S->rec) { b->err = "the call's result arrays were left on the device (FQ_EMIT_DEVICE_ONLY)"; return FQ_EINVAL; }
-  if (S->n_surv > 0 && !hb.has_qual()) { b->err = "the batch carries no qualities"; return FQ_EINVAL; }
-  // records are independent of each other: ranges of pairs are formatted on several threads and handed to the BGZF layer in order
-  auto format_range = [&](int lo, int hi, std::vector<uint8_t> &dst) {
-  for (int sp = lo; sp < hi; ++sp) {
-    if (S->rec[2 * (size_t)sp].type == FQ_TYPE_NO_MATCH && S->rec[2 * (size_t)sp + 1].type == FQ_TYPE_NO_MATCH) continue;
-    if (ao->single_end) {   // SingleEndMapper's BAM branch (src/BwtMapper.cpp:1372-1387): AddAlignment(p, 0), SetSamRecord(p, 0)
-      FqRead p = S->read(2 * (size_t)sp);
-      int seqid;
-      const int j = (int)(ref_end(p) - p.pos);
-      fq_coor_pac2real(b->ix, p.pos, j, &seqid);
-      if ((int64_t)p.pos + j - b->ix->contigs[seqid].offset > b->ix->contigs[seqid].len) p.type = FQ_TYPE_NO_MATCH;
-      b->record(dst, ao, hb, S->n_pairs, p, p, true);
-      continue;
-    }
-    FqRead p = S->read(2 * (size_t)sp), q = S->read(2 * (size_t)sp + 1);
-    for (FqRead *r : {&p, &q})   // StatCollector::AddAlignment first (src/StatCollector.cpp:955-971)
-      if (r->type != FQ_TYPE_NO_MATCH) {
-        int seqid;
-        const int j = (int)(ref_end(*r) - r->pos);
-        fq_coor_pac2real(b->ix, r->pos, j, &seqid);
-        if ((int64_t)r->pos + j - b->ix->contigs[seqid].offset > b->ix->contigs[seqid].len) r->type = FQ_TYPE_NO_MATCH;
-      }
-    b->record(dst, ao, hb, S->n_pairs, p, q);
-    if (p.type == FQ_TYPE_NO_MATCH && q.type != FQ_TYPE_NO_MATCH) { p.pos = q.pos; p.strand = q.strand; }   // what the first call left in p (:991-994)
-    b->record(dst, ao, hb, S->n_pairs, q, p);
-  }
-  };
-  const int T = S->n_surv >= 256 ? 8 : 1;
-  parts.assign((size_t)T, std::vector<uint8_t>());
-  if (T == 1) format_range(0, S->n_surv, parts[0]);
-  else {
-    std::vector<std::thread> th;
-    const int per = (S->n_surv + T - 1) / T;
-    for (int t = 0; t < T; ++t) { const int lo = t * per, hi = std::min(S->n_surv, lo + per); if (lo < hi) th.emplace_back(format_range, lo, hi, std::ref(parts[(size_t)t])); }
-    for (auto &x : th) x.join();
-  }
+// the BAM branch of PairEndMapper's consumer loop over one batch (src/BwtMapper.cpp:2054-2085): the batch's records, in input order, in b->last
+static int format_last(fq_bam_t *b, fq_ctx_t *c) {
+  FqBamArgs A{};
+  if (const int rc = fq_ctx_host_view(c, &A.s)) { b->err = fq_ctx_last_error(c); return rc; }
+  A.ctg_rid = b->ctg_rid.data(); A.ctg_g0 = b->ctg_g0.data(); A.rg = b->rg_id.c_str(); A.rg_len = (int32_t)b->rg_id.size();
+  const size_t N = 2 * (size_t)A.s.n_surv;
+  std::vector<uint32_t> len(N + 1), meta(N + 1);
+  std::vector<uint64_t> off(N + 1);
+  A.len = len.data(); A.meta = meta.data(); A.off = off.data(); A.split = 0;
+  fq_host_records(A.s.n_surv, [&](int idx) { fq_bam_len_thread(A, idx); });
+  uint64_t total = 0;
+  for (size_t i = 0; i < N; ++i) { off[i] = total; total += len[i]; }
+  b->last.resize((size_t)total);
+  A.out = b->last.data();
+  fq_host_records(A.s.n_surv, [&](int idx) { fq_bam_fill_thread(A, idx); });
   return FQ_OK;
 }
 extern "C" int fq_bam_add_last(fq_bam_t *b, fq_ctx_t *c) {
@@ -445,10 +246,9 @@ extern "C" int fq_bam_add_last(fq_bam_t *b, fq_ctx_t *c) {
     if (n < 0) { b->err = "fq_bam_add_last: fetching the records from the device failed"; return (int)n; }
     return b->z.ok ? FQ_OK : FQ_EIO;
   }
-  std::vector<std::vector<uint8_t>> parts;
-  const int rc = format_last(b, c, parts);
+  const int rc = format_last(b, c);
   if (rc) return rc;
-  for (auto &part : parts) if (!part.empty()) b->z.write(part.data(), part.size());
+  if (!b->last.empty()) b->z.write(b->last.data(), b->last.size());
   return b->z.ok ? FQ_OK : FQ_EIO;
 }
 // The same records as bytes (uncompressed BAM records, block_size first), for a caller that writes them itself or elsewhere: several
@@ -464,11 +264,8 @@ extern "C" int fq_bam_format_last(fq_bam_t *b, fq_ctx_t *c, const void **data, i
     *data = b->last.data(); *len = (int64_t)b->last.size();
     return FQ_OK;
   }
-  std::vector<std::vector<uint8_t>> parts;
-  const int rc = format_last(b, c, parts);
+  const int rc = format_last(b, c);
   if (rc) return rc;
-  b->last.clear();
-  for (auto &part : parts) b->last.insert(b->last.end(), part.begin(), part.end());
   *data = b->last.data(); *len = (int64_t)b->last.size();
   return FQ_OK;
 }

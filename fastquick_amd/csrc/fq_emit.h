@@ -1,8 +1,9 @@
-// fq_emit.h -- the consumers of a call's records ON THE DEVICE: the SAM text of bwa_print_sam1 (libbwa/bwase.c:455-581) and what StatCollector
-// does with every pair (src/StatCollector.cpp:424-1101) as kernels over the result arrays of the call, which are resident when stage F has
-// written them (fq_records.h: fq_flat_fill_thread).  Round 5 formatted and counted on the host: 2.8 us per surviving pair for the SAM text and 3.8 us
-// for the statistics, against 0.03 us per pair of device time for the alignment itself -- on on-target input the command line ran at a hundredth
-// of the kernels' rate.
+// fq_emit.h -- the consumers of a call's records, stated ONCE for the device and the host: the SAM text of bwa_print_sam1 (libbwa/bwase.c:455-581), the BAM
+// record of SetSamRecord (src/BwtMapper.cpp:977-1264) and what StatCollector does with every pair (src/StatCollector.cpp:424-1101), as routines over the flat
+// result arrays of the call (fq_records.h: fq_flat_fill_thread).  On the device they run as kernels over the arrays where stage F has written them; the host
+// formatters (fq_sam.cpp, fq_bam.cpp) loop over the same routines on the arrays that landed on the host (fq_ctx_host_view).  Round 5 formatted and counted on the
+// host only: 2.8 us per surviving pair for the SAM text and 3.8 us for the statistics, against 0.03 us per pair of device time for the alignment itself -- on
+// on-target input the command line ran at a hundredth of the kernels' rate.
 //
 //   SAM text      a thread per record measures its line, a prefix sum places the lines, a thread per record writes its line: one D2H of text
 //                 (fq_sam_line: ONE routine for both passes, so that a line is as long as it was measured)
@@ -12,7 +13,7 @@
 //                 outputs -- .InsertSizeTable lines, the markers' pileup entries -- are measured, placed by prefix sums and written in input order,
 //                 so that the host only appends them
 //
-// Every body is a FQ_HD function of (args, index); fq_device.hip wraps each in a __global__ kernel, tests/emu loops over it.
+// Every body is a FQ_HD function of (args, index); fq_device.hip wraps each in a __global__ kernel, tests/emu and the host formatters loop over it.
 // Reference citations are paths under the Griffan/FASTQuick tree.
 #pragma once
 #include "fq_kernels.h"
@@ -325,7 +326,7 @@ FQ_HD void fq_sam_body_piece(const FqSamArgs &A, int idx, int c) {
   for (int t = 0; t < FQ_SAM_PIECE && b0 + t < n; ++t) dst[t] = fq_sam_body_char(B, b0 + t);
 }
 
-// ---- BAM records: SetSamRecord (src/BwtMapper.cpp:977-1264), restated field by field as fq_bam.cpp does on the host -----------------------
+// ---- BAM records: SetSamRecord (src/BwtMapper.cpp:977-1264), field by field; fq_bam.cpp keeps the header, the BGZF layer and the loop ------
 struct FqBamArgs {
   FqSamArgs s;
   const int32_t *ctg_rid;        // [n contigs] id of the contig's chromosome among the BAM header's references (-1: not there)

@@ -485,16 +485,15 @@ extern "C" int fq_index_load(const char *prefix_c, int device_ordinal, fq_index_
   if (fqdev::h2d(ix->d_pac, ix->pac.data(), ix->pac.size()) || fqdev::sync()) return fail(FQ_ENODEV);
   ix->dev.pac = (const uint8_t *)ix->d_pac;
   ix->dev.l_pac = ix->l_pac;
-  {   // the contig table and the N holes, for the consumers on the device (fq_emit.h)
+  {   // the contig table and the N holes, for the consumers (fq_emit.h): kept on the host, and a copy in HBM
     const size_t nc = ix->contigs.size(), nh = ix->holes.size();
-    std::vector<int64_t> off(nc), hoff(nh + 1, 0);
-    std::vector<int32_t> len(nc), hlen(nh + 1, 0);
-    std::vector<uint32_t> noff(nc + 1, 0);
-    std::string names;
-    for (size_t i = 0; i < nc; ++i) { off[i] = ix->contigs[i].offset; len[i] = ix->contigs[i].len; noff[i] = (uint32_t)names.size(); names += ix->contigs[i].name; }
-    noff[nc] = (uint32_t)names.size();
-    names.push_back(0);
-    for (size_t i = 0; i < nh; ++i) { hoff[i] = ix->holes[i].offset; hlen[i] = ix->holes[i].len; }
+    fq_index::ContigTable &T = ix->ctab;
+    T.off.resize(nc); T.len.resize(nc); T.name_off.assign(nc + 1, 0); T.hole_off.assign(nh + 1, 0); T.hole_len.assign(nh + 1, 0);
+    for (size_t i = 0; i < nc; ++i) { T.off[i] = ix->contigs[i].offset; T.len[i] = ix->contigs[i].len; T.name_off[i] = (uint32_t)T.names.size(); T.names += ix->contigs[i].name; }
+    T.name_off[nc] = (uint32_t)T.names.size();
+    T.names.push_back(0);
+    for (size_t i = 0; i < nh; ++i) { T.hole_off[i] = ix->holes[i].offset; T.hole_len[i] = ix->holes[i].len; }
+    ix->host_contigs = FqDevContigs{(int32_t)nc, (int32_t)nh, T.off.data(), T.len.data(), T.name_off.data(), T.names.data(), T.hole_off.data(), T.hole_len.data()};
     auto up = [&](const void *src, size_t bytes) -> void * {
       void *d = fqdev::dmalloc(bytes ? bytes : 16);
       if (d) { ix->load_scratch.push_back(d); if (bytes && fqdev::h2d(d, src, bytes)) return nullptr; }
@@ -502,9 +501,9 @@ extern "C" int fq_index_load(const char *prefix_c, int device_ordinal, fq_index_
     };
     FqDevContigs &C = ix->dev_contigs;
     C.n = (int32_t)nc; C.n_holes = (int32_t)nh;
-    C.off = (const int64_t *)up(off.data(), nc * 8); C.len = (const int32_t *)up(len.data(), nc * 4);
-    C.name_off = (const uint32_t *)up(noff.data(), (nc + 1) * 4); C.names = (const char *)up(names.data(), names.size());
-    C.hole_off = (const int64_t *)up(hoff.data(), (nh + 1) * 8); C.hole_len = (const int32_t *)up(hlen.data(), (nh + 1) * 4);
+    C.off = (const int64_t *)up(T.off.data(), nc * 8); C.len = (const int32_t *)up(T.len.data(), nc * 4);
+    C.name_off = (const uint32_t *)up(T.name_off.data(), (nc + 1) * 4); C.names = (const char *)up(T.names.data(), T.names.size());
+    C.hole_off = (const int64_t *)up(T.hole_off.data(), (nh + 1) * 8); C.hole_len = (const int32_t *)up(T.hole_len.data(), (nh + 1) * 4);
     if (!C.off || !C.len || !C.name_off || !C.names || !C.hole_off || !C.hole_len || fqdev::sync()) return fail(FQ_ENODEV);
   }
   mark("FM index, SA, pac staged");
@@ -627,29 +626,4 @@ extern "C" int fq_index_contig(const fq_index_t *ix, int32_t id, const char **na
   return FQ_OK;
 }
 
-int fq_coor_pac2real(const fq_index *ix, int64_t pos, int len, int *seqid) {
-  int left = 0, mid = 0, right = (int)ix->contigs.size(), nn = 0;
-  const int ns = right;
-  while (left < right) {
-    mid = (left + right) >> 1;
-    if (pos >= ix->contigs[mid].offset) {
-      if (mid == ns - 1) break;
-      if (pos < ix->contigs[mid + 1].offset) break;
-      left = mid + 1;
-    } else right = mid;
-  }
-  *seqid = mid;
-  left = 0; right = (int)ix->holes.size();
-  while (left < right) {
-    const int m = (left + right) >> 1;
-    const FqHole &h = ix->holes[m];
-    if (pos >= h.offset + h.len) left = m + 1;
-    else if (pos + len <= h.offset) right = m;
-    else {
-      if (pos >= h.offset) nn += h.offset + h.len < pos + len ? (int)(h.offset + h.len - pos) : len;
-      else nn += h.offset + h.len < pos + len ? h.len : (int)(len - (h.offset - pos));
-      break;
-    }
-  }
-  return nn;
-}
+int fq_coor_pac2real(const fq_index *ix, int64_t pos, int len, int *seqid) { return fq_dev_pac2real(ix->host_contigs, pos, len, seqid); }

@@ -26,6 +26,13 @@ struct fq_index {
   std::vector<FqHole> holes;
   // host copies kept for the (host-side) consumers
   std::vector<uint8_t> pac;
+  struct ContigTable {          // the contigs and the N holes as flat arrays: what host_contigs points at and dev_contigs is a copy of
+    std::vector<int64_t> off, hole_off;
+    std::vector<int32_t> len, hole_len;
+    std::vector<uint32_t> name_off;
+    std::string names;
+  } ctab;
+  FqDevContigs host_contigs{};  // ... for fq_emit.h's routines run over host memory (the host formatters, fq_coor_pac2real)
   // device
   FqDevIndex dev{};
   FqDevContigs dev_contigs{};   // contig table and N holes in HBM (the consumers on the device: fq_emit.h)

@@ -142,6 +142,19 @@ struct FqHostReads {
   }
 };
 FqHostReads fq_ctx_host_reads(const fq_ctx_t *c);
+// The last call as the routines of fq_emit.h read it, with every pointer in host memory: what the host formatters (fq_sam.cpp, fq_bam.cpp) loop
+// over.  Valid until the next call on the context.  FQ_EINVAL (and the context's error text) when the call left no result arrays on the host
+// (FQ_EMIT_DEVICE_ONLY) or its batch carries no qualities.
+int fq_ctx_host_view(fq_ctx_t *c, FqSamArgs *a);
+// ... and the loop: fn(idx) for every record of the call, over up to 8 ranges of pairs on threads of their own (records are independent of each other)
+template <class F>
+void fq_host_records(int n_surv, F fn) {
+  const int T = n_surv >= 256 ? 8 : 1, per = (n_surv + T - 1) / T;
+  std::vector<std::thread> th;
+  for (int t = 1; t < T; ++t) th.emplace_back([=] { for (int idx = 2 * t * per; idx < 2 * std::min(n_surv, (t + 1) * per); ++idx) fn(idx); });
+  for (int idx = 0; idx < 2 * std::min(n_surv, per); ++idx) fn(idx);
+  for (auto &x : th) x.join();
+}
 // What a call that counted on the device (fq_ctx_attach_qc) leaves for the consumer's host side: the order-dependent outputs in input order,
 // the call's counters.  NULL: the context has no consumer attached.
 struct fq_qc;
@@ -170,6 +183,6 @@ void fq_qc_gate_leave(fq_qc *q);
 int64_t fq_ctx_qc_stream(fq_ctx_t *c, int which, fq_sink_fn sink, void *user);
 int fq_ctx_emit_wait(fq_ctx_t *c);       // the last call's consumer kernels were only enqueued: wait for them (before its counts / sizes are read)
 int64_t fq_ctx_last_bases(const fq_ctx_t *c);   // sum of the read lengths of the last batch (NumBase increment)
-// the name a record prints under (fq_sam.cpp): `/1` `/2` stripped, a revived mate under its partner's name
+// the name a record prints under (fq_emit_name over the batch's names, fq_sam.cpp)
 std::string fq_read_name(const FqHostReads *hb, int pair, int end, bool revived);
 const fq_opts_t *fq_ctx_opts(const fq_ctx_t *c);

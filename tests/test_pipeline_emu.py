@@ -183,6 +183,51 @@ def test_emulated_pipeline_matches_oracle_with_option_variants(name, okw, emu_li
     al.close(); ix.close(); oa.close()
 
 
+def test_host_formatter_reads_every_input_kind(emu_lib, tmp_path):
+    """The host formatter loops over fq_emit.h's fq_sam_line on a host view of the call whose bases come from where the input kind
+    leaves them: the caller's rows (ASCII batch), the survivors' rows decoded from the 2-bit body plus the exception list (packed
+    batch), the compact rows that came back from the device (text-resident batch, fq_align_text).  All three must be the oracle's
+    bwa_print_sam1 text.  The reads are the il13_trim variant's (n_rate=0.004, 700 pairs, Phred+64, trimming), not golden trim76:
+    that case has no N among its reads, so its exception list is empty."""
+    from fastquick_amd import synth
+    okw = dict(mode=1 | 2 | 0x200, trim_qual=15)
+    ref = synth.make_reference(n_markers=60, n_long=6, seed=35, repeat_every=2, tandem_every=7)
+    pre = str(tmp_path / "ref.FASTQuick.fa")
+    ref.write_fasta(pre)
+    api.build_index(pre, lib=emu_lib)
+    rb = synth.make_reads(ref, 700, on_target=0.95, seed=45, sub_rate=0.03, del_frac=0.08, ins_frac=0.07, n_rate=0.004, indel_len_max=3, chimera_frac=0.06, qual_decay=True)
+    rb.qual[rb.qual > 0] += 31
+    assert sum(int((rb.seq[e, i, :rb.lens[e, i]] == ord("N")).sum()) for e in range(2) for i in range(700)) > 100
+    oa = ob.OracleAligner(pre, ob.default_opts(**okw))
+    oa.align(rb.names, rb.seq, rb.qual, rb.lens, None, str(tmp_path / "orc.sam"), batch=400)
+    oa.close()
+    want = open(str(tmp_path / "orc.sam"), "rb").read()
+    ix = api.Index(pre, lib=emu_lib)
+    for kind in ("ascii", "packed"):
+        al = api.Aligner(ix, api.default_opts(emu_lib, **okw), max_pairs=400)
+        api.align_stream(al, rb.names, rb.seq, rb.qual, rb.lens, 400, None, str(tmp_path / (kind + ".sam")), packed=kind == "packed")
+        al.close()
+        assert open(str(tmp_path / (kind + ".sam")), "rb").read() == want, kind
+    fq = []
+    for e in range(2):
+        fq.append(str(tmp_path / ("reads_%d.fq.gz" % (e + 1))))
+        text = b"".join(b"@" + bytes(rb.names[i]) + b"\n" + bytes(rb.seq[e, i, :rb.lens[e, i]]) + b"\n+\n" + bytes(rb.qual[e, i, :rb.lens[e, i]]) + b"\n" for i in range(700))
+        with open(fq[e], "wb") as fh:
+            fh.write(synth.bgzf_compress(text, threads=2, level=6, member=4000))
+    fe = api.DeviceFrontEnd(fq[0], fq[1], batch_pairs=400, chunk_pairs=400, slot_mode=0, max_read_len=160, lib=emu_lib)
+    al = api.Aligner(ix, api.default_opts(emu_lib, batch_pairs=400, **okw), max_pairs=400)
+    got = [ix.sam_header()]
+    while True:
+        n, b = fe.next()
+        if n <= 0:
+            break
+        al.align_text(b)
+        got.append(al.sam_text())
+        fe.release(b)
+    fe.close(); al.close(); ix.close()
+    assert n == 0 and b"".join(got) == want, "text-resident"
+
+
 def trimmed_max_len_case(lib, tmp_path, device=None):
     """infer_isize's max_len is the longest TRIMMED read of the reference batch, filtered reads included (bwape.c:60-61).  Short
     fragments make the estimate's lower bound equal to it (p25 - 2 IQR < max_len), so it shows in the result.  Every on-target
