@@ -2157,10 +2157,10 @@ int emit_measure(Call &K) {
     { const int rc = fq_qc_device_prepare(c->qc, &a, K.n_surv); if (rc) { c->err = std::string("the QC consumer could not take the call: ") + fq_qc_last_error(c->qc); return rc; } }
     const size_t NC = (size_t)FQ_C_STRIPES * FQ_C_STRIDE;
     CKM(c->d_qadded.ensure(N + 1) && c->d_istlen.ensure(P + 1) && c->d_istoff.ensure(P + 2) && c->d_ptcnt.ensure(N + 1) && c->d_ptoff.ensure(N + 2) && c->d_qcnt.ensure(NC) && c->p_qcnt.ensure(NC));
-    if (a.shard) { CKM(c->d_dupkey.ensure(P + 1) && c->p_dupkey.ensure(P + 1)); }
+    if (a.list_keys) { CKM(c->d_dupkey.ensure(P + 1) && c->p_dupkey.ensure(P + 1)); }
     CK(fqdev::dzero(c->d_qcnt.p, NC * 8));
     a.counters = c->d_qcnt.p; a.added = c->d_qadded.p; a.ist_len = c->d_istlen.p; a.ist_off = c->d_istoff.p; a.pt_cnt = c->d_ptcnt.p; a.pt_off = c->d_ptoff.p;
-    a.dup_key = a.shard ? c->d_dupkey.p : nullptr;
+    a.dup_key = a.list_keys ? c->d_dupkey.p : nullptr;
     CK(fqdev::launch_qc(FQ_QOP_PAIR, a, (int64_t)P));
     CK(fqdev::launch_scan(c->d_istlen.p, c->d_istoff.p, (uint32_t)P));
     CK(fqdev::launch_scan(c->d_ptcnt.p, c->d_ptoff.p, (uint32_t)N));
@@ -2226,9 +2226,9 @@ int emit_fill(Call &K) {
     CK(fqdev::launch_qc(FQ_QOP_BASE, a, (int64_t)N));
     // (the lines and the pileup entries stay in HBM: the consumer's host side fetches them in slices beside the next call -- fq_ctx_qc_stream)
     CK(fqdev::copy_pinned(c->p_qcnt.p, c->d_qcnt.p, NC * 8, 0));
-    if (a.shard) CK(fqdev::copy_pinned(c->p_dupkey.p, c->d_dupkey.p, P * 8, 0));
-    c->stats.d2h_bytes += NC * 8 + (a.shard ? P * 8 : 0);
-    c->qc_out.ist_bytes = E.ist_total; c->qc_out.n_pile = E.pt_total; c->qc_out.dup_key = a.shard ? c->p_dupkey.p : nullptr;
+    if (a.list_keys) CK(fqdev::copy_pinned(c->p_dupkey.p, c->d_dupkey.p, P * 8, 0));
+    c->stats.d2h_bytes += NC * 8 + (a.list_keys ? P * 8 : 0);
+    c->qc_out.ist_bytes = E.ist_total; c->qc_out.n_pile = E.pt_total; c->qc_out.dup_key = a.list_keys ? c->p_dupkey.p : nullptr;
     c->qc_out.ready = true;
   }
   CK(fqdev::copy_flush_now());

@@ -1,8 +1,9 @@
 // fq_emit.h -- the consumers of a call's records, stated ONCE for the device and the host: the SAM text of bwa_print_sam1 (libbwa/bwase.c:455-581), the BAM
 // record of SetSamRecord (src/BwtMapper.cpp:977-1264) and what StatCollector does with every pair (src/StatCollector.cpp:424-1101), as routines over the flat
-// result arrays of the call (fq_records.h: fq_flat_fill_thread).  On the device they run as kernels over the arrays where stage F has written them; the host
-// formatters (fq_sam.cpp, fq_bam.cpp) loop over the same routines on the arrays that landed on the host (fq_ctx_host_view).  Round 5 formatted and counted on the
-// host only: 2.8 us per surviving pair for the SAM text and 3.8 us for the statistics, against 0.03 us per pair of device time for the alignment itself -- on
+// result arrays of the call (fq_records.h: fq_flat_fill_thread).  One statement, two loops: on the device the routines run as kernels over the arrays where stage F
+// has written them; the host side of every consumer (fq_sam.cpp, fq_bam.cpp, fq_qc.cpp) loops over the same routines on the arrays that landed on the host
+// (fq_ctx_host_view).  There is no second statement to hold this one to: what pins it is the reference's own output (tests/golden, the soak against oracle/_ref).
+// Round 5 formatted and counted on the host only: 2.8 us per surviving pair for the SAM text and 3.8 us for the statistics, against 0.03 us per pair of device time for the alignment itself -- on
 // on-target input the command line ran at a hundredth of the kernels' rate.
 //
 //   SAM text      a thread per record measures its line, a prefix sum places the lines, a thread per record writes its line: one D2H of text
@@ -13,7 +14,7 @@
 //                 outputs -- .InsertSizeTable lines, the markers' pileup entries -- are measured, placed by prefix sums and written in input order,
 //                 so that the host only appends them
 //
-// Every body is a FQ_HD function of (args, index); fq_device.hip wraps each in a __global__ kernel, tests/emu and the host formatters loop over it.
+// Every body is a FQ_HD function of (args, index); fq_device.hip wraps each in a __global__ kernel, tests/emu and the consumers' host sides loop over it.
 // Reference citations are paths under the Griffan/FASTQuick tree.
 #pragma once
 #include "fq_kernels.h"
@@ -580,7 +581,7 @@ FQ_HD void fq_bam_body_piece(const FqBamArgs &A, int idx, int c) {
 enum { FQ_EOP_SAM_LEN = 0, FQ_EOP_SAM_FILL, FQ_EOP_BAM_LEN, FQ_EOP_BAM_FILL, FQ_EOP_SAM_BODY, FQ_EOP_BAM_BODY, FQ_EOP_COUNT };
 
 // =====================================================================================================================================
-// StatCollector on the device: AddAlignment (src/StatCollector.cpp:950-1101), AddSingleAlignment (:424-620), ProcessPairStatus (:623-921)
+// StatCollector: AddAlignment (src/StatCollector.cpp:950-1101), AddSingleAlignment (:424-620), ProcessPairStatus (:623-921)
 // =====================================================================================================================================
 #if defined(__HIP_DEVICE_COMPILE__)
 #define FQ_ATOMIC_INC32(p) atomicAdd((unsigned int *)(p), 1u)
@@ -589,8 +590,8 @@ enum { FQ_EOP_SAM_LEN = 0, FQ_EOP_SAM_FILL, FQ_EOP_BAM_LEN, FQ_EOP_BAM_FILL, FQ_
 #define FQ_ATOMIC_MIN64_PLAIN(p, v) atomicMin((unsigned long long *)(p), (unsigned long long)(v))
 #define FQ_ATOMIC_CAS64(p, cmp, v) atomicCAS((unsigned long long *)(p), (unsigned long long)(cmp), (unsigned long long)(v))
 #else
-#define FQ_ATOMIC_INC32(p) (++*(p))
-#define FQ_ATOMIC_DEC32(p) (--*(p))
+#define FQ_ATOMIC_INC32(p) __atomic_fetch_add((p), 1u, __ATOMIC_RELAXED)               /* (the host loop's threads share the depth tables) */
+#define FQ_ATOMIC_DEC32(p) __atomic_fetch_add((p), 0xffffffffu, __ATOMIC_RELAXED)
 #define FQ_ATOMIC_ADD64_PLAIN(p, v) (*(p) += (v))
 #define FQ_ATOMIC_MIN64_PLAIN(p, v) (*(p) = *(p) < (uint64_t)(v) ? *(p) : (uint64_t)(v))
 static inline uint64_t fq_host_cas64(uint64_t *p, uint64_t cmp, uint64_t v) { const uint64_t old = *p; if (old == cmp) *p = v; return old; }
@@ -619,7 +620,7 @@ struct FqQcArgs {
   FqSamArgs s;                   // the call's records, reads and names (text / len / off unused)
   FqDevIndex ix;                 // the 2-bit reference
   FqQcGeom g;
-  int32_t cal_dup, shard;
+  int32_t cal_dup, list_keys;    // list_keys: the proper pairs' duplicate keys go to dup_key in pair order, not into dup_tab (a shard consumer, whose keys the merge looks up; the host loop)
   uint64_t ord_base;             // pairs the consumer has seen before this call (orders the first counts of the sex-chromosome contigs)
   // the consumer's tables
   uint32_t *depth, *q20, *q30;   // over the flank positions.  depth: a DIFFERENCE table (+1 where a run of counted positions begins, -1 behind its end; modulo 2^32); q20 / q30: the counted bases BELOW the threshold
@@ -630,8 +631,8 @@ struct FqQcArgs {
   uint64_t *counters;            // striped like the work counters (FQ_C_STRIPES x FQ_C_STRIDE)
   uint32_t *sex_cnt;             // [n contigs][4] overlapped, fully, pair_overlapped, fully_paired
   uint64_t *sex_first;           // [n contigs] key of the first count (2 * pair ordinal + which), ~0: never
-  uint64_t *dup_tab; uint64_t dup_mask;   // open-addressing set of the proper pairs' keys (start << 32 | end); a shard consumer lists its keys instead:
-  uint64_t *dup_key;             // [n_surv] key or ~0 (shard)
+  uint64_t *dup_tab; uint64_t dup_mask;   // open-addressing set of the proper pairs' keys (start << 32 | end); or the keys are listed instead:
+  uint64_t *dup_key;             // [n_surv] key or ~0 (list_keys)
   // per call
   int32_t *added;                // [2 n_surv] the contig of a record that went through AddSingleAlignment, or -1
   uint32_t *ist_len; const uint64_t *ist_off; char *ist_text;      // .InsertSizeTable lines per pair
@@ -651,7 +652,9 @@ FQ_HD void fq_dupset_rehash_thread(const uint64_t *old, uint64_t *tab, uint64_t 
   if (old[i] != FQ_QC_DUP_EMPTY) (void)fq_dupset_insert(tab, mask, old[i]);
 }
 
-// a mate as the .InsertSizeTable sees it (MateSpan of fq_qc.cpp)
+// A mate as the .InsertSizeTable sees it: where its alignment starts and stops on the concatenated reference once the left soft clip is taken back (32-bit
+// arithmetic, as the reference's bwtint_t: it wraps for a hit hanging over the start), on which contig, and how much room that contig leaves on the side the
+// insert grows to (fq_span_room: the upper bound of an insert that starts at this forward mate / ends at this reverse mate; -1: the mate itself leaves the contig)
 struct FqSpan {
   fq_result_t r;
   int idx, type, present, placed;
@@ -751,7 +754,7 @@ FQ_HD void fq_pair_status(const FqQcArgs &A, int sp, int tP, int tQ, int type, b
     // the duplicate key: contig and both outer ends ("%d:%d:%d" in the reference).  A proper pair's ends lie inside its contig, so the ends alone name it.
     const uint64_t key = (uint64_t)(uint32_t)start << 32 | (uint64_t)(uint32_t)end;
     if (keyed) {
-      if (A.shard) A.dup_key[sp] = key;
+      if (A.list_keys) A.dup_key[sp] = key;
       else dup = fq_dupset_insert(A.dup_tab, A.dup_mask, key);
     }
     FQ_WAVE_COUNT(&A.counters[FQ_QC_C_PROPER], keyed);
@@ -759,7 +762,7 @@ FQ_HD void fq_pair_status(const FqQcArgs &A, int sp, int tP, int tQ, int type, b
   }
 }
 
-// the reference bases a read covers, block by block (for_match_blocks of fq_qc.cpp): f(absoluteSite, length, cycle, onRead, onRef) per M block
+// the reference bases a read covers, block by block: (absoluteSite, length, cycle, onRead, onRef) per M block of its CIGAR (AddSingleAlignment's walk, :455-600)
 struct FqBlockIter {
   const uint16_t *cg; int n_cigar, k;
   int strand, sign, absolute, cyc, on_read, on_ref, len;
@@ -912,7 +915,6 @@ FQ_HD void fq_qc_pair_core(const FqQcArgs &A, int sp, bool effects, FqTxt &o) {
     A.added[2 * sp + e] = seqid;           // (the per-base kernel starts from the contig: no search of its own)
     A.pt_cnt[2 * sp + e] = n;
   }
-  if (A.shard && A.dup_key && A.ist_len[sp] == 0) { /* (no line: no key either) */ }
   FQ_WAVE_COUNT(&A.counters[FQ_QC_C_UNMAPPED], unmapped);
   FQ_WAVE_COUNT(&A.counters[FQ_QC_C_RETAINED1], retained == 1);
   FQ_WAVE_COUNT(&A.counters[FQ_QC_C_RETAINED2], retained == 2);
@@ -920,7 +922,7 @@ FQ_HD void fq_qc_pair_core(const FqQcArgs &A, int sp, bool effects, FqTxt &o) {
   FQ_WAVE_COUNT(&A.counters[FQ_QC_C_FAILED2], failed == 2);
 }
 FQ_HD void fq_qc_pair_thread(const FqQcArgs &A, int sp) {
-  if (A.shard) A.dup_key[sp] = FQ_QC_DUP_EMPTY;
+  if (A.list_keys) A.dup_key[sp] = FQ_QC_DUP_EMPTY;
   FqTxt o; o.dst = nullptr; o.at = 0;
   fq_qc_pair_core(A, sp, true, o);
 }

@@ -146,15 +146,19 @@ FqHostReads fq_ctx_host_reads(const fq_ctx_t *c);
 // over.  Valid until the next call on the context.  FQ_EINVAL (and the context's error text) when the call left no result arrays on the host
 // (FQ_EMIT_DEVICE_ONLY) or its batch carries no qualities.
 int fq_ctx_host_view(fq_ctx_t *c, FqSamArgs *a);
-// ... and the loop: fn(idx) for every record of the call, over up to 8 ranges of pairs on threads of their own (records are independent of each other)
+// ... and the loop: the records of the call as up to FQ_HOST_RANGES ranges of pairs on threads of their own (records are independent of each other).
+// fn(t, lo, hi): range t holds records [lo, hi)
+enum { FQ_HOST_RANGES = 8 };
 template <class F>
-void fq_host_records(int n_surv, F fn) {
-  const int T = n_surv >= 256 ? 8 : 1, per = (n_surv + T - 1) / T;
+void fq_host_ranges(int n_surv, F fn) {
+  const int T = n_surv >= 256 ? FQ_HOST_RANGES : 1, per = (n_surv + T - 1) / T;
   std::vector<std::thread> th;
-  for (int t = 1; t < T; ++t) th.emplace_back([=] { for (int idx = 2 * t * per; idx < 2 * std::min(n_surv, (t + 1) * per); ++idx) fn(idx); });
-  for (int idx = 0; idx < 2 * std::min(n_surv, per); ++idx) fn(idx);
+  for (int t = 1; t < T; ++t) th.emplace_back([=] { fn(t, 2 * std::min(n_surv, t * per), 2 * std::min(n_surv, (t + 1) * per)); });
+  fn(0, 0, 2 * std::min(n_surv, per));
   for (auto &x : th) x.join();
 }
+template <class F>
+void fq_host_records(int n_surv, F fn) { fq_host_ranges(n_surv, [=](int, int lo, int hi) { for (int idx = lo; idx < hi; ++idx) fn(idx); }); }      // fn(idx) per record
 // What a call that counted on the device (fq_ctx_attach_qc) leaves for the consumer's host side: the order-dependent outputs in input order,
 // the call's counters.  NULL: the context has no consumer attached.
 struct fq_qc;
@@ -183,6 +187,4 @@ void fq_qc_gate_leave(fq_qc *q);
 int64_t fq_ctx_qc_stream(fq_ctx_t *c, int which, fq_sink_fn sink, void *user);
 int fq_ctx_emit_wait(fq_ctx_t *c);       // the last call's consumer kernels were only enqueued: wait for them (before its counts / sizes are read)
 int64_t fq_ctx_last_bases(const fq_ctx_t *c);   // sum of the read lengths of the last batch (NumBase increment)
-// the name a record prints under (fq_emit_name over the batch's names, fq_sam.cpp)
-std::string fq_read_name(const FqHostReads *hb, int pair, int end, bool revived);
 const fq_opts_t *fq_ctx_opts(const fq_ctx_t *c);

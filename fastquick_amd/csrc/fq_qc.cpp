@@ -1,10 +1,15 @@
 // fq_qc.cpp -- the QC consumer of the alignment records: what StatCollector does with every pair that
 // BwtMapper::PairEndMapper hands it (src/BwtMapper.cpp:2047-2050 / 2075-2079) and the files its ProcessCore writes
-// (src/StatCollector.cpp:2012-2028).  Restated from the reference's behaviour, function by function:
+// (src/StatCollector.cpp:2012-2028).
+// What happens to a pair is stated ONCE, in fq_emit.h (AddAlignment :950-1101, AddSingleAlignment :424-620, ProcessPairStatus
+// :623-921 as FQ_HD routines), and run by two loops: the kernels of a context the consumer is attached to (fq_ctx_attach_qc), and
+// the host loop below (fq_qc::host_call) over the arrays of a call that landed on the host (fq_ctx_host_view).  Both leave the same
+// forms -- sums in tables, lines and pileup entries in input order, counters, duplicate keys -- and this file turns them into the
+// consumer's state with one piece of code each (fold, take_lines, take_piles, take_keys, add_counts).  What holds the 13 files
+// to the reference is the reference's own output (tests/golden, the soak against oracle/_ref), on both loops; the loops agreeing
+// with each other would show nothing, they run the same text.
+// Restated here from the reference's behaviour, function by function:
 //   RestoreVcfSites      src/StatCollector.cpp:1742-1839   marker / dbSNP / GC tables, flank regions
-//   AddAlignment         :950-1101     contig-end un-mapping (Q10), which mates are added, sex-chromosome counters
-//   AddSingleAlignment   :424-620      per-base depth / quality / cycle statistics and marker pileups
-//   ProcessPairStatus    :623-921      one .InsertSizeTable line per pair, insert sizes, PCR duplicates
 //   GetDepthDist .. SummaryOutput  :1858-2028, 2343-2483   the output files
 // Containers whose iteration order reaches an output (.SexChromInfo: an unordered_map walked in bucket order) are the same
 // standard containers, filled in the same order, so the files come out byte for byte; the others are order-free sums.
@@ -19,7 +24,6 @@
 #include <map>
 #include <sstream>
 #include <string>
-#include <thread>
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
@@ -35,7 +39,6 @@
 
 namespace {
 const int kInsertLimit = 4096;                 // INSERT_SIZE_LIMIT
-const char kSign[2] = {1, -1};
 
 std::string chrom_key(std::string chr) {       // upper case, a name containing "CHR" loses its first three characters (:1760-1764)
   std::transform(chr.begin(), chr.end(), chr.begin(), ::toupper);
@@ -84,61 +87,6 @@ struct FileStat {                               // FileStatCollector, src/StatCo
   std::string f1, f2;
 };
 
-// a record as AddAlignment sees it: the bwa_seq_t fields it reads
-struct Rec {
-  const FqRead *r = nullptr;
-  int type = 0;
-  std::string name;
-  int64_t end() const {                         // pos_end, libbwa/bwase.c:420-432
-    if (!r->cigar.empty()) { int64_t x = r->pos; for (uint16_t g : r->cigar) { const int op = g >> 14; if (op == FQ_OP_M || op == FQ_OP_D) x += g & 0x3fff; } return x; }
-    return (int64_t)r->pos + r->len;
-  }
-};
-
-std::string cigar_string(const FqRead &p) {     // Cigar2String, :58-72
-  std::string s;
-  for (uint16_t g : p.cigar) { s += std::to_string(g & 0x3fff); s.push_back("MIDS"[g >> 14]); }
-  if (p.cigar.empty()) s = std::to_string(p.len) + "M";
-  return s;
-}
-
-// The reference bases under a read's aligned blocks, from the read, its CIGAR and its MD tag (what RecoverRefseqByMDandCigar
-// returns, src/StatCollector.cpp:98-205): the bases of the M blocks in order, then the MD tag walked left to right -- a number
-// skips that many matching bases, a letter replaces the base it stands for, '^' + letters puts deleted reference bases back in.
-// An MD tag that is one number equal to the read's length means "the read is the reference".
-std::string recover_ref(const std::string &read, std::string md, const std::vector<uint16_t> &cigar) {
-  for (char &ch : md) ch = (char)toupper((unsigned char)ch);
-  if (md.find_first_of("ATCGN") == std::string::npos && atol(md.c_str()) == (long)read.size()) return read;
-  std::string ref;
-  if (cigar.empty()) ref = read;
-  else {
-    size_t on_read = 0;
-    for (uint16_t g : cigar) {
-      const size_t n = g & 0x3fff;
-      const int op = g >> 14;
-      if (op == FQ_OP_M) ref.append(read, on_read, n);
-      if (op != FQ_OP_D) on_read += n;
-    }
-  }
-  size_t at = 0;                       // bases of `ref` the tag has accounted for
-  for (size_t i = 0; i < md.size();) {
-    size_t run = 0;
-    while (i < md.size() && isdigit((unsigned char)md[i])) run = run * 10 + (size_t)(md[i++] - '0');
-    if (i >= md.size()) break;
-    at += run;
-    if (md[i] == '^') {
-      size_t j = ++i;
-      while (j < md.size() && !isdigit((unsigned char)md[j])) ++j;
-      ref.insert(std::min(at, ref.size()), md, i, j - i);
-      at += j - i;
-      i = j;
-    } else {
-      if (at < ref.size()) ref[at] = md[i];
-      ++at; ++i;
-    }
-  }
-  return ref;
-}
 }  // namespace
 
 struct fq_qc {
@@ -149,7 +97,20 @@ struct fq_qc {
   struct Marker { std::string chrom_raw, id, ref, alt, qual, filter, info; int pos = 0; };
   std::vector<Marker> markers;
   std::map<std::string, std::map<int, unsigned>> vcf_table;
-  std::unordered_map<std::string, std::unordered_map<int, unsigned>> dbsnp;
+  // ... flattened for fq_emit.h's routines (the vectors FqQcGeom points into; restore() ends with flatten()): the host loop reads them where they are,
+  // device_setup uploads them
+  struct Flat {
+    std::vector<int32_t> ctg_chrom, ctg_g0, ctg_reg_lo, chr_reg0, reg_start, reg_end, chr_mk0, mk_pos;
+    std::vector<uint32_t> reg_base, mk_idx;
+    std::vector<uint8_t> ctg_sex, dbsnp;
+  } flat;
+  template <class P> FqQcGeom geom_through(P p) const {      // p(vector): where the caller's routines find its elements
+    FqQcGeom g;
+    g.ctg_chrom = p(flat.ctg_chrom); g.ctg_g0 = p(flat.ctg_g0); g.ctg_reg_lo = p(flat.ctg_reg_lo); g.ctg_sex = p(flat.ctg_sex);
+    g.chr_reg0 = p(flat.chr_reg0); g.reg_start = p(flat.reg_start); g.reg_end = p(flat.reg_end); g.reg_base = p(flat.reg_base);
+    g.chr_mk0 = p(flat.chr_mk0); g.mk_pos = p(flat.mk_pos); g.mk_idx = p(flat.mk_idx); g.dbsnp = p(flat.dbsnp);
+    return g;
+  }
   // GC content per position: the reference keeps a hash of every position of every marker's window (a later marker's window writes over an
   // earlier one's where they overlap) and reads it at the positions of the flank regions only (GetDepthDist; a position no window covers
   // reads 0): kept here as one byte per flank-region position, laid out like the depth tables
@@ -188,13 +149,41 @@ struct fq_qc {
   }
   std::string out_prefix;
   std::ofstream table;
-  // ---- the consumer's tables on the device (fq_emit.h): set up by the first call of a context this consumer is attached to (fq_ctx_attach_qc);
-  //      the sums stay there until pull() adds them to the tables above (fq_qc_write, fq_qc_state_export)
+  // ---- the sums in the form fq_emit.h's routines keep them (FqQcArgs): the host loop's between its calls, or what pull() fetched from the device.
+  //      fold() adds them to the tables above (fq_qc_write, fq_qc_state_export, fq_qc_state_reset)
+  struct Sums {
+    std::vector<uint32_t> depth, q20, q30, sex_cnt;
+    std::vector<uint64_t> hist, insert, est, sex_first;
+    void zero(size_t T, size_t nc) {
+      depth.assign(T + 1, 0); q20.assign(T + 1, 0); q30.assign(T + 1, 0); sex_cnt.assign((nc + 1) * 4, 0);
+      hist.assign(4 * 256, 0); insert.assign((size_t)kInsertLimit, 0); est.assign(4 * (size_t)kInsertLimit, 0); sex_first.assign(nc + 1, ~0ull);
+    }
+  } host_sums;                                     // (empty until the first host call)
+  void fold(const Sums &s);
+  // ... and what a call leaves beside them, from either loop
+  void take_lines(const char *text, size_t n) { table.write(text, (std::streamsize)n); }      // .InsertSizeTable lines, in input order
+  void take_piles(const FqPileEntry *e, size_t n) {                                           // pileup entries, in input order
+    for (; n; --n, ++e) {
+      seq_vec[e->k] += (char)e->base; qual_vec[e->k] += (char)e->qual;
+      cycle_vec[e->k].push_back(e->cyc); maq_vec[e->k].push_back(e->maq); strand_vec[e->k].push_back(e->strand != 0);
+    }
+  }
+  void take_keys(const uint64_t *keys, int n_surv, bool count_repeats);
+  void add_counts(const uint64_t *cnt) {                                                      // FQ_QC_C_*
+    cur.BwaUnmapped += (long long)cnt[FQ_QC_C_UNMAPPED];
+    cur.TotalRetained += (long long)(cnt[FQ_QC_C_RETAINED1] + 2 * cnt[FQ_QC_C_RETAINED2]);
+    cur.TotalMAPQ += (long long)(cnt[FQ_QC_C_FAILED1] + 2 * cnt[FQ_QC_C_FAILED2]);
+    NumPairReads += 2 * cnt[FQ_QC_C_PROPER];
+    NumPCRDup += 2 * cnt[FQ_QC_C_DUP];
+  }
+  void host_call(FqQcArgs &a);
+  // ---- the consumer's tables on the device: set up by the first call of a context this consumer is attached to (fq_ctx_attach_qc);
+  //      the sums stay there until pull() fetches them
   std::mutex dev_mu;
   bool dev_on = false;
   bool device_adds = false, host_adds = false;    // a consumer counts its records on one side only (the duplicate set lives there)
   fqdev::State *dev = nullptr;                     // this object's own streams: pull / reset from any thread
-  std::vector<void *> d_bufs;                      // geometry
+  std::vector<void *> d_bufs;                      // the upload of `flat`
   FqQcGeom geom{};
   size_t table_size = 0, n_contigs = 0;
   uint32_t *d_depth = nullptr, *d_q20 = nullptr, *d_q30 = nullptr, *d_sex_cnt = nullptr;
@@ -210,25 +199,13 @@ struct fq_qc {
   std::condition_variable gate_cv;
   uint64_t tickets = 0, serving = 0;
   int device_setup();
-  int pull();                                      // device sums -> host tables; the device tables start again from zero
+  int pull();                                      // both loops' sums -> the tables above; theirs start again from zero
   int bind_own();
   ~fq_qc() { if (dev_on || dev) { if (!bind_own()) { for (void *b : d_bufs) fqdev::dfree(b); for (void *b : {(void *)d_depth, (void *)d_q20, (void *)d_q30, (void *)d_sex_cnt, (void *)d_hist, (void *)d_insert, (void *)d_sex_first, (void *)d_dup, (void *)d_est}) fqdev::dfree(b); } if (dev) fqdev::state_destroy(dev); } }
 
   int restore(const std::string &ref_prefix);
-  bool add_single(const Rec &p, const FqHostReads &hb);
-  struct MateSpan;
-  MateSpan mate_span(const Rec *R, bool placed) const;
-  int pair_status(const Rec *p, const Rec *q, int type);
-  struct ReadGeom;
-  struct StatHist { size_t EmpRep[256] = {}, EmpCycle[256] = {}, misEmpRep[256] = {}, misEmpCycle[256] = {}; };
-  std::vector<const FqRead *> stat_jobs;   // reads whose per-base statistics are still to be added (valid until the batch's records go away)
-  FqWorkPool pool;                         // ... and the workers they are spread over
-  bool read_geom(const Rec &P, ReadGeom &g) const;
-  void read_stats(const FqRead &p, const FqHostReads &hb, StatHist &h);
-  void run_stat_jobs(const FqHostReads &hb, int threads);
-  int add_alignment(Rec &p, Rec &q, const FqHostReads &hb, long long &total_add_failed);
-  int add_alignment_se(Rec &p, const FqHostReads &hb, long long &total_add_failed);   // AddAlignment(p, q = 0): the single-end mapper's call
-  const char *contig_name(int seqid) const { return ix->contigs[seqid].name.c_str(); }
+  void flatten(const std::unordered_map<std::string, std::unordered_map<int, unsigned>> &dbsnp);
+  FqWorkPool pool;                         // the workers fq_qc_write spreads the markers' lines over
 };
 
 int fq_qc::restore(const std::string &ref_prefix) {
@@ -281,6 +258,7 @@ int fq_qc::restore(const std::string &ref_prefix) {
       memcpy(gc_flat.data() + it->second.second + (size_t)(a - it->first), gc_bytes.data() + w.at + (size_t)(a - lo), (size_t)(b - a + 1));
     }
   }
+  std::unordered_map<std::string, std::unordered_map<int, unsigned>> dbsnp;
   while (std::getline(db, line)) {
     if (line.empty() || line[0] == '#') continue;
     std::stringstream ss(line);
@@ -288,303 +266,34 @@ int fq_qc::restore(const std::string &ref_prefix) {
     std::getline(ss, c, '\t'); std::getline(ss, pos, '\t');
     dbsnp[chrom_key(c)][atoi(pos.c_str())] = 1;
   }
+  flatten(dbsnp);
   return FQ_OK;
 }
 
-// AddSingleAlignment, :424-620 (the reduced-reference branch: contig names `CHR:POS@REF/ALT[|L]`), in two parts:
-//  * what depends on the order of the reads -- the pileup strings of the markers a read covers (UpdateInfoVecAtMarker) -- here,
-//    in input order;
-//  * the per-base statistics (UpdateInfoVecAtRegularSite / StatVecDistUpdate: depth, Q20 / Q30 depth, quality and cycle
-//    histograms, mismatch counts) are sums, so the reads are queued (stat_jobs) and fq_qc_add_last spreads them over threads once
-//    the batch has been walked.  A StatCollector pass over an on-target batch was 40x the batch's alignment time.
-struct fq_qc::ReadGeom { int seqid, readRealStart; std::string chrom; };
-bool fq_qc::read_geom(const Rec &P, ReadGeom &g) const {
-  const FqRead &p = *P.r;
-  g.seqid = 0;
-  fq_coor_pac2real(ix, p.pos, (int)(P.end() - p.pos), &g.seqid);
-  const std::string &chrName = ix->contigs[g.seqid].name;
-  const int pos = (int)((int64_t)p.pos - ix->contigs[g.seqid].offset + 1);
-  const size_t colon = chrName.find(':');
-  if (colon == std::string::npos) return false;          // (external alignments are not this path)
-  const size_t at = chrName.find('@');
-  const int refCoord = (int)strtol(chrName.substr(colon + 1, at - colon + 1).c_str(), nullptr, 10);
-  const int fl = chrName[chrName.size() - 1] == 'L' ? o.flank_long_len : o.flank_len;
-  g.readRealStart = refCoord - fl + pos - 1;
-  g.chrom = chrom_key(chrName.substr(0, colon));         // AddMatchBaseInfo, :362-379
-  return true;
-}
-template <class F> static void for_match_blocks(const FqRead &p, int readRealStart, F f) {   // f(absoluteSite, length, cycle, onRead, onRef) per M block
-  int absoluteSite = readRealStart, tmpCycle = p.strand != 0 ? p.full_len - 1 : 0, onRead = 0, onRef = 0;
-  if (!p.cigar.empty()) {
-    for (uint16_t g : p.cigar) {
-      const int cl = g & 0x3fff, op = g >> 14;
-      if (op == FQ_OP_M) { f(absoluteSite, cl, tmpCycle, onRead, onRef); absoluteSite += cl; tmpCycle += cl * kSign[p.strand]; onRead += cl; onRef += cl; }
-      else if (op == FQ_OP_S) { tmpCycle += cl * kSign[p.strand]; onRead += cl; }
-      else if (op == FQ_OP_D) { absoluteSite += cl; onRef += cl; }
-      else { tmpCycle += cl * kSign[p.strand]; onRead += cl; }
-    }
-  } else f(absoluteSite, (int)p.len, tmpCycle, onRead, onRef);
-}
-bool fq_qc::add_single(const Rec &P, const FqHostReads &hb) {
-  const FqRead &p = *P.r;
-  if (P.type == FQ_TYPE_NO_MATCH || p.mapQ < 20) return false;
-  ReadGeom g;
-  if (!read_geom(P, g)) return false;
-  const auto vt = vcf_table.find(g.chrom);
-  if (vt != vcf_table.end()) {
-    uint8_t codes[FQ_LMAX + 8];
-    bool have = false;
-    const uint8_t *hq = nullptr;
-    const int qsub = (o.mode & FQ_MODE_IL13) ? 31 : 0;    // qualities are kept 31 lower in --I mode (src/BwtMapper.cpp:549-553)
-    for_match_blocks(p, g.readRealStart, [&](int absoluteSite, int cl, int tmpCycle, int onRead, int) {
-      // UpdateInfoVecAtMarker, :339-360: the markers inside [absoluteSite, absoluteSite + cl), in increasing position
-      for (auto hit = vt->second.lower_bound(absoluteSite); hit != vt->second.end() && hit->first < absoluteSite + cl; ++hit) {
-        if (!have) { hb.codes((size_t)p.r, p.full_len, codes); hq = hb.qual((size_t)p.r); have = true; }
-        const int d = hit->first - absoluteSite, cyc = tmpCycle + d * kSign[p.strand], rr = onRead + d;
-        const unsigned k = hit->second;
-        char base, ql;      // the read in the orientation of the reference (SetSamRecord's strings)
-        if (p.strand == 0) { const int cc = codes[rr]; base = "ACGTN"[cc > 4 ? 4 : cc]; ql = (char)(hq[rr] - qsub - 33); }
-        else { const int cc = codes[p.full_len - 1 - rr]; base = "TGCAN"[cc > 4 ? 4 : cc]; ql = (char)(hq[p.full_len - 1 - rr] - qsub - 33); }
-        seq_vec[k] += base; qual_vec[k] += ql;
-        cycle_vec[k].push_back(cyc); maq_vec[k].push_back((unsigned char)(p.mapQ + 33)); strand_vec[k].push_back(p.strand != 0);
-      }
-    });
-  }
-  stat_jobs.push_back(P.r);
-  return true;
-}
-// the per-base statistics of one queued read; `h` = this thread's quality / cycle histograms (summed afterwards), the depth tables
-// are shared and updated atomically
-void fq_qc::read_stats(const FqRead &p, const FqHostReads &hb, StatHist &h) {
-  Rec P; P.r = &p; P.type = p.type;
-  ReadGeom g;
-  if (!read_geom(P, g)) return;
-  uint8_t codes[FQ_LMAX + 8];
-  hb.codes((size_t)p.r, p.full_len, codes);
-  const uint8_t *hq = hb.qual((size_t)p.r);
-  const int qsub = (o.mode & FQ_MODE_IL13) ? 31 : 0;
-  std::string seq, qual;
-  seq.reserve((size_t)p.full_len); qual.reserve((size_t)p.full_len);
-  if (p.strand == 0) for (int j = 0; j != p.full_len; ++j) { seq += "ACGTN"[codes[j] > 4 ? 4 : codes[j]]; qual += (char)(hq[j] - qsub - 33); }
-  else for (int j = 0; j != p.full_len; ++j) { const int c = codes[p.full_len - 1 - j]; seq += "TGCAN"[c > 4 ? 4 : c]; qual += (char)(hq[p.full_len - 1 - j] - qsub - 33); }
-  const std::string refSeq = recover_ref(seq, p.md, p.cigar);
-  const auto fl_it = flank_idx.find(g.chrom);
-  const auto db_it = dbsnp.find(g.chrom);
-  int f_lo = 1, f_hi = 0;          // the region the previous position fell into (consecutive positions mostly share it)
-  size_t f_base = 0;
-  auto in_flank = [&](int pos) {   // RegionList::IsOverlapped, :48-66
-    if (pos >= f_lo && pos <= f_hi) return true;
-    if (fl_it == flank_idx.end()) return false;
-    auto lo = fl_it->second.lower_bound(pos);
-    if (lo != fl_it->second.end() && lo->first <= pos && lo->second.first >= pos) { f_lo = lo->first; f_hi = lo->second.first; f_base = lo->second.second; return true; }
-    if (lo != fl_it->second.begin()) { --lo; if (lo->first <= pos && lo->second.first >= pos) { f_lo = lo->first; f_hi = lo->second.first; f_base = lo->second.second; return true; } }
-    return false;
-  };
-  for_match_blocks(p, g.readRealStart, [&](int absoluteSite, int cl, int tmpCycle, int onRead, int onRef) {
-    // UpdateInfoVecAtRegularSite, :381-422
-    int cyc = tmpCycle, rr = onRead, rf = onRef;
-    for (int i = absoluteSite; i != absoluteSite + cl; ++i, cyc += kSign[p.strand], ++rr, ++rf) {
-      if (!in_flank(i)) continue;
-      const char refBase = rf >= 0 && (size_t)rf < refSeq.size() ? refSeq[rf] : 0, readBase = seq[rr], baseQual = qual[rr];
-      const size_t k = f_base + (size_t)(i - f_lo);
-      __atomic_fetch_add(&depth[k], 1u, __ATOMIC_RELAXED);
-      if (baseQual >= 20) { __atomic_fetch_add(&q20[k], 1u, __ATOMIC_RELAXED); if (baseQual >= 30) __atomic_fetch_add(&q30[k], 1u, __ATOMIC_RELAXED); }
-      // StatVecDistUpdate, :304-317
-      ++h.EmpRep[(unsigned char)baseQual];
-      ++h.EmpCycle[(unsigned char)cyc];
-      if (readBase != 'N' && refBase != readBase && refBase != 'N' && (db_it == dbsnp.end() || db_it->second.find(i) == db_it->second.end())) {
-        ++h.misEmpRep[(unsigned char)baseQual];
-        ++h.misEmpCycle[(unsigned char)cyc];
-      }
-    }
-  });
-}
-// the queued reads of a batch over `threads` threads
-void fq_qc::run_stat_jobs(const FqHostReads &hb, int threads) {
-  const size_t n = stat_jobs.size();
-  if (!n) return;
-  const int T = n >= 512 ? std::max(1, threads) : 1;
-  std::vector<StatHist> hist((size_t)T);
-  auto work = [&](size_t lo, size_t hi, int t) { for (size_t j = lo; j < hi; ++j) read_stats(*stat_jobs[j], hb, hist[(size_t)t]); };
-  if (T == 1) work(0, n, 0);
-  else {
-    const size_t per = (n + (size_t)T - 1) / (size_t)T;
-    pool.run(T, [&](int t) { const size_t lo = (size_t)t * per, hi = std::min(n, lo + per); if (lo < hi) work(lo, hi, t); });
-  }
-  for (const StatHist &h : hist)
-    for (int v = 0; v < 256; ++v) { EmpRep[v] += h.EmpRep[v]; EmpCycle[v] += h.EmpCycle[v]; misEmpRep[v] += h.misEmpRep[v]; misEmpCycle[v] += h.misEmpCycle[v]; }
-  stat_jobs.clear();
-}
-
-// ---- one .InsertSizeTable line per pair, and what it feeds: the insert-size histogram and the duplicate set -----------------------
-// (the semantics are ProcessPairStatus', src/StatCollector.cpp:623-921: the file format, the histogram and the duplicate key are fixed
-// by byte-for-byte output; the arrangement below is this file's)
-//
-// A mate as the table sees it: where its alignment starts and stops on the concatenated reference once the left soft clip is taken
-// back (32-bit arithmetic, as the reference's bwtint_t: it wraps for a hit hanging over the start), on which contig, and how much
-// room that contig leaves on the side the insert grows to.
-struct fq_qc::MateSpan {
-  const FqRead *r = nullptr;
-  const std::string *name = nullptr;
-  int contig = -1, flag = 0, clip_left = 0, clip_right = 0;
-  int64_t start = 0, stop = 0, contig_lo = 0, contig_hi = 0;
-  std::string cigar;
-  bool present() const { return r != nullptr; }
-  bool reverse() const { return r->strand != 0; }
-  // upper bound of an insert that starts at this forward mate / ends at this reverse mate; -1: the mate itself leaves the contig
-  int room() const { return reverse() ? (contig_hi >= stop ? (int)(stop - contig_lo) : -1) : (start >= contig_lo ? (int)(contig_hi - start) : -1); }
-  void columns(std::ostream &o, bool placed) const {        // contig, 1-based position, flag, length, CIGAR -- or the row of an absent / unplaced mate
-    if (placed) o << "\t" << contig_name << "\t" << (int64_t)r->pos - contig_lo + 1 << "\t" << flag << "\t" << r->len << "\t" << cigar;
-    else o << "\t*\t*\t" << flag << "\t" << 0 << "\t*";
-  }
-  const char *contig_name = "";
-};
-fq_qc::MateSpan fq_qc::mate_span(const Rec *R, bool placed) const {
-  MateSpan m;
-  if (!R) return m;
-  m.r = R->r; m.name = &R->name;
-  m.flag = m.r->extra_flag | (R->type == FQ_TYPE_NO_MATCH ? 4 : 0) | (m.r->strand ? 16 : 0);
-  if (!placed) return m;
-  fq_coor_pac2real(ix, m.r->pos, (int)(R->end() - m.r->pos), &m.contig);
-  m.contig_name = contig_name(m.contig);
-  m.contig_lo = ix->contigs[m.contig].offset; m.contig_hi = m.contig_lo + (int64_t)ix->contigs[m.contig].len;
-  if (!m.r->cigar.empty()) {
-    if ((m.r->cigar.front() >> 14) == FQ_OP_S) m.clip_left = m.r->cigar.front() & 0x3fff;
-    if ((m.r->cigar.back() >> 14) == FQ_OP_S) m.clip_right = m.r->cigar.back() & 0x3fff;
-  }
-  m.start = (int64_t)(uint32_t)(m.r->pos - (uint32_t)m.clip_left);
-  m.stop = (int64_t)(uint32_t)(m.r->pos - (uint32_t)m.clip_left + (uint32_t)m.r->len);
-  m.cigar = cigar_string(*m.r);
-  return m;
-}
-// type: 0 only the first mate is placed, 1 both, 2 only the second.  Returns 2 when the pair counts as low quality (TotalMAPQ), else 0.
-int fq_qc::pair_status(const Rec *P, const Rec *Q, int type) {
-  const MateSpan a = mate_span(P, type != 2), b = mate_span(Q, type != 0);
-  auto line = [&](const std::string &name, int lim_fwd, int lim_rev, int insert, const char *outcome) {
-    table << name << "\t" << lim_fwd << "\t" << lim_rev << "\t" << insert;
-    a.columns(table, type != 2);
-    b.columns(table, type != 0);
-    table << "\t" << outcome << std::endl;
-  };
-  if (type != 1) {                                  // one mate placed: its own room on its contig is all the table can say
-    const MateSpan &m = type == 0 ? a : b;
-    if (m.r->mapQ == 0) { line(*m.name, -1, -1, -1, "LowQual"); return 2; }
-    const int room = m.room();
-    if (room < 0) return 2;                         // (no line either: the reference returns before it writes one)
-    line(*m.name, m.reverse() ? -1 : room, m.reverse() ? room : -1, -1, m.reverse() ? "RevOnly" : "FwdOnly");
-    return 0;
-  }
-  // both placed: a pair is a forward mate followed by a reverse mate
-  const MateSpan *fwd = nullptr, *rev = nullptr;
-  if (!a.reverse() && b.reverse() && a.r->pos < b.r->pos) { fwd = &a; rev = &b; }
-  else if (!b.reverse() && a.reverse() && b.r->pos < a.r->pos) { fwd = &b; rev = &a; }
-  if (!fwd) { line(*a.name, -1, -1, -1, "NotPair"); return 0; }
-  const int lim_fwd = std::min(fwd->room(), kInsertLimit - 1), lim_rev = std::min(rev->room(), kInsertLimit - 1);
-  if (a.contig != b.contig) { ++InsertDist[0]; line(*a.name, lim_fwd, lim_rev, -1, "NotPair"); return 0; }
-  if (a.r->mapQ == 0 || b.r->mapQ == 0) { line(*a.name, lim_fwd, lim_rev, -1, "LowQual"); return 2; }
-  const int start = (int)(uint32_t)fwd->start, end = (int)(uint32_t)rev->stop, insert = end - start;
-  const bool proper = lim_fwd != -1 && lim_rev != -1, unclipped = fwd->clip_left == 0 && rev->clip_right == 0;
-  if (insert >= 0 && insert < kInsertLimit) ++InsertDist[insert];   // (the reference indexes unchecked; inserts beyond the table are out of its bounds)
-  line(*a.name, lim_fwd, lim_rev, insert, proper ? "PropPair" : "PartialPair");
-  if (proper && unclipped) {                        // the duplicate key: contig and both outer ends
-    char key[1024];
-    snprintf(key, sizeof key, "%d:%d:%d", a.contig, start, end);
-    if (!dup_table.insert(std::string(key)).second) NumPCRDup += 2;
-    NumPairReads += 2;
-    if (shard) dup_log.emplace_back(key);
-  }
-  return 0;
-}
-
-// AddAlignment, :950-1101
-int fq_qc::add_alignment(Rec &P, Rec &Q, const FqHostReads &hb, long long &failed) {
-  int seqid = 0, seqid2 = 0;
-  auto bridge = [&](Rec &R, int &id) {
-    if (R.type == FQ_TYPE_NO_MATCH) return;
-    const int j = (int)(R.end() - R.r->pos);
-    fq_coor_pac2real(ix, R.r->pos, j, &id);
-    if ((int64_t)R.r->pos + j - ix->contigs[id].offset > ix->contigs[id].len) R.type = FQ_TYPE_NO_MATCH;
-  };
-  bridge(P, seqid);
-  bridge(Q, seqid2);
-  auto partial = [](const Rec &R) { for (uint16_t g : R.r->cigar) if ((g >> 14) == FQ_OP_S) return true; return false; };
-  auto sex = [](const std::string &n) { return n.find('Y') != std::string::npos || n.find('X') != std::string::npos; };
-  const std::string qname = contig_name(seqid2);
-  if (P.type == FQ_TYPE_NO_MATCH) {
-    if (add_single(Q, hb)) {
-      if (sex(qname)) { ++cs(qname).overlapped; if (!partial(Q)) ++cs(qname).fully; }
-      pair_status(&P, &Q, 2);
-      failed += 1;
-      return 1;
-    }
-    failed += 2;
-    return 0;
-  }
-  const std::string pname = contig_name(seqid);
-  if (Q.type == FQ_TYPE_NO_MATCH) {
-    if (add_single(P, hb)) {
-      if (sex(pname)) { ++cs(pname).overlapped; if (!partial(P)) ++cs(pname).fully; }
-      pair_status(&P, &Q, 0);
-      failed += 1;
-      return 1;
-    }
-    failed += 2;
-    return 0;
-  }
-  if (partial(P)) {
-    if (sex(qname)) {
-      if (partial(Q)) ++cs(qname).overlapped;
-      else { ++cs(qname).overlapped; ++cs(qname).fully; }
-      if (pname == qname) ++cs(qname).pair_overlapped;
-      ++cs(pname).overlapped;
-    }
-  } else if (sex(qname)) {
-    if (partial(Q)) { ++cs(qname).overlapped; if (pname == qname) ++cs(qname).pair_overlapped; }
-    else {
-      ++cs(qname).overlapped; ++cs(qname).fully;
-      if (pname == qname) { ++cs(qname).pair_overlapped; ++cs(qname).fully_paired; }
-    }
-    ++cs(pname).overlapped; ++cs(pname).fully;
-  }
-  if (pair_status(&P, &Q, 1) != 1 || o.cal_dup) {
-    if (add_single(P, hb)) {
-      if (add_single(Q, hb)) return 2;
-      failed += 1;
-      return 1;
-    }
-    if (add_single(Q, hb)) { failed += 1; return 1; }
-    failed += 2;
-    return 0;
-  }
-  failed += 2;
-  return 0;
-}
-
-// ---- the device side ---------------------------------------------------------------------------------------------------------
-int fq_qc::bind_own() {
-  if (!dev) dev = fqdev::state_create(ix->device);
-  if (!dev || fqdev::bind(dev)) { err = std::string("QC consumer: no device state: ") + fqdev::last_error(); return FQ_ENODEV; }
-  return FQ_OK;
-}
-// RestoreVcfSites' tables flattened for the kernels (FqQcGeom), the sums zeroed.  Runs on the calling context's bound state.
-int fq_qc::device_setup() {
-  if (dev_on) return FQ_OK;
+// RestoreVcfSites' tables as fq_emit.h's routines read them (FqQcGeom): per contig its chromosome, its place in the genome (AddSingleAlignment's
+// readRealStart, :424-440; AddMatchBaseInfo's chromosome key, :362-379) and where a read's walk over the flank regions starts; per chromosome its flank
+// regions and markers in increasing position; the known variant sites as a flag per flank position
+void fq_qc::flatten(const std::unordered_map<std::string, std::unordered_map<int, unsigned>> &dbsnp) {
   const size_t nc = ix->contigs.size();
   n_contigs = nc;
+  table_size = depth.size();
   std::vector<std::string> chroms;                  // the chromosomes of the flank regions (the markers' chromosomes: the same keys)
   std::map<std::string, int> chrom_id;
   for (const auto &kv : flank_idx) { chrom_id[kv.first] = (int)chroms.size(); chroms.push_back(kv.first); }
   for (const auto &kv : vcf_table) if (!chrom_id.count(kv.first)) { chrom_id[kv.first] = (int)chroms.size(); chroms.push_back(kv.first); }
-  std::vector<int32_t> ctg_chrom(nc), ctg_g0(nc), ctg_reg_lo(nc, 0), chr_reg0(chroms.size() + 1, 0), reg_start, reg_end, chr_mk0(chroms.size() + 1, 0), mk_pos;
-  std::vector<uint8_t> ctg_sex(nc);
-  std::vector<uint32_t> reg_base, mk_idx;
+  std::vector<int32_t> &ctg_chrom = flat.ctg_chrom, &ctg_g0 = flat.ctg_g0, &ctg_reg_lo = flat.ctg_reg_lo, &chr_reg0 = flat.chr_reg0, &reg_start = flat.reg_start, &reg_end = flat.reg_end,
+                       &chr_mk0 = flat.chr_mk0, &mk_pos = flat.mk_pos;
+  std::vector<uint32_t> &reg_base = flat.reg_base, &mk_idx = flat.mk_idx;
+  std::vector<uint8_t> &ctg_sex = flat.ctg_sex, &db = flat.dbsnp;
+  ctg_chrom.assign(nc, 0); ctg_g0.assign(nc, 0); ctg_reg_lo.assign(nc, 0); ctg_sex.assign(nc, 0);
+  chr_reg0.assign(chroms.size() + 1, 0); chr_mk0.assign(chroms.size() + 1, 0);
   for (size_t i = 0; i < nc; ++i) {
     const std::string &nm = ix->contigs[i].name;
     ctg_sex[i] = nm.find('Y') != std::string::npos || nm.find('X') != std::string::npos;
     const size_t colon = nm.find(':');
     if (colon == std::string::npos) { ctg_chrom[i] = -2; ctg_g0[i] = 0; continue; }
     const size_t at = nm.find('@');
-    const int refCoord = (int)strtol(nm.substr(colon + 1, at - colon + 1).c_str(), nullptr, 10);     // read_geom
+    const int refCoord = (int)strtol(nm.substr(colon + 1, at - colon + 1).c_str(), nullptr, 10);
     const int fl = nm[nm.size() - 1] == 'L' ? o.flank_long_len : o.flank_len;
     ctg_g0[i] = refCoord - fl;
     auto it = chrom_id.find(chrom_key(nm.substr(0, colon)));
@@ -605,8 +314,7 @@ int fq_qc::device_setup() {
     const int first = ctg_g0[i];               // (genome coordinate of offset 0 of the contig; a read's bases lie at or behind it)
     ctg_reg_lo[i] = (int32_t)(std::lower_bound(reg_end.begin() + r0, reg_end.begin() + r1, first) - reg_end.begin());
   }
-  table_size = depth.size();
-  std::vector<uint8_t> db(table_size + 1, 0);
+  db.assign(table_size + 1, 0);
   for (const auto &kv : flank_idx) {                 // the known variant sites that lie in a flank region (the only positions the statistics look at)
     auto di = dbsnp.find(kv.first);
     if (di == dbsnp.end()) continue;
@@ -617,6 +325,18 @@ int fq_qc::device_setup() {
       if (site.first >= r->first && site.first <= r->second.first) db[r->second.second + (size_t)(site.first - r->first)] = 1;
     }
   }
+}
+
+// ---- the device side ---------------------------------------------------------------------------------------------------------
+int fq_qc::bind_own() {
+  if (!dev) dev = fqdev::state_create(ix->device);
+  if (!dev || fqdev::bind(dev)) { err = std::string("QC consumer: no device state: ") + fqdev::last_error(); return FQ_ENODEV; }
+  return FQ_OK;
+}
+// the geometry uploaded, the sums zeroed.  Runs on the calling context's bound state.
+int fq_qc::device_setup() {
+  if (dev_on) return FQ_OK;
+  const size_t nc = n_contigs;
   bool ok = true;
   auto up = [&](const void *src, size_t bytes) -> void * {
     void *d = fqdev::dmalloc(bytes ? bytes : 16);
@@ -625,12 +345,7 @@ int fq_qc::device_setup() {
     if (bytes && fqdev::h2d(d, src, bytes)) ok = false;
     return d;
   };
-  geom.ctg_chrom = (const int32_t *)up(ctg_chrom.data(), nc * 4); geom.ctg_g0 = (const int32_t *)up(ctg_g0.data(), nc * 4); geom.ctg_sex = (const uint8_t *)up(ctg_sex.data(), nc);
-  geom.ctg_reg_lo = (const int32_t *)up(ctg_reg_lo.data(), nc * 4);
-  geom.chr_reg0 = (const int32_t *)up(chr_reg0.data(), chr_reg0.size() * 4); geom.reg_start = (const int32_t *)up(reg_start.data(), reg_start.size() * 4);
-  geom.reg_end = (const int32_t *)up(reg_end.data(), reg_end.size() * 4); geom.reg_base = (const uint32_t *)up(reg_base.data(), reg_base.size() * 4);
-  geom.chr_mk0 = (const int32_t *)up(chr_mk0.data(), chr_mk0.size() * 4); geom.mk_pos = (const int32_t *)up(mk_pos.data(), mk_pos.size() * 4);
-  geom.mk_idx = (const uint32_t *)up(mk_idx.data(), mk_idx.size() * 4); geom.dbsnp = (const uint8_t *)up(db.data(), db.size());
+  geom = geom_through([&](const auto &v) { return (decltype(v.data()))up(v.data(), v.size() * sizeof v[0]); });
   auto zeroed = [&](size_t bytes, int fill) -> void * {
     void *d = fqdev::dmalloc(bytes ? bytes : 16);
     if (!d) { ok = false; return nullptr; }
@@ -666,7 +381,7 @@ int fq_qc_device_prepare(fq_qc *q, FqQcArgs *a, int n_surv) {
     }
   }
   a->g = q->geom;
-  a->cal_dup = q->o.cal_dup; a->shard = q->shard ? 1 : 0;
+  a->cal_dup = q->o.cal_dup; a->list_keys = q->shard ? 1 : 0;
   a->ord_base = q->ord_next;
   q->ord_next += (uint64_t)n_surv;
   a->depth = q->d_depth; a->q20 = q->d_q20; a->q30 = q->d_q30; a->hist = q->d_hist; a->insert_dist = q->d_insert;
@@ -677,38 +392,103 @@ int fq_qc_device_prepare(fq_qc *q, FqQcArgs *a, int n_surv) {
 uint64_t fq_qc_gate_ticket(fq_qc *q) { std::lock_guard<std::mutex> lk(q->gate_mu); return q->tickets++; }
 void fq_qc_gate_enter(fq_qc *q, uint64_t ticket) { std::unique_lock<std::mutex> lk(q->gate_mu); q->gate_cv.wait(lk, [&] { return q->serving == ticket; }); }
 void fq_qc_gate_leave(fq_qc *q) { { std::lock_guard<std::mutex> lk(q->gate_mu); ++q->serving; } q->gate_cv.notify_all(); }
-// what the device has summed since the last pull, added to the host's tables
+// What the two loops have summed since the last pull, added to the consumer's tables; theirs start again from zero.
 int fq_qc::pull() {
   std::lock_guard<std::mutex> lk(dev_mu);
+  if (!host_sums.depth.empty()) { fold(host_sums); host_sums.zero(table_size, n_contigs); }
   if (!dev_on) return FQ_OK;
   int rc = bind_own();
   if (rc) return rc;
-  const size_t T = table_size, nc = n_contigs;
-  std::vector<uint32_t> d(T + 1), a(T + 1), b(T + 1), sc((nc + 1) * 4);
-  std::vector<uint64_t> hist(4 * 256), ins((size_t)kInsertLimit), first(nc + 1), est(4 * (size_t)kInsertLimit);
-  if (fqdev::d2h(d.data(), d_depth, (T + 1) * 4) || fqdev::d2h(a.data(), d_q20, (T + 1) * 4) || fqdev::d2h(b.data(), d_q30, (T + 1) * 4) || fqdev::d2h(hist.data(), d_hist, hist.size() * 8) ||
-      fqdev::d2h(ins.data(), d_insert, ins.size() * 8) || fqdev::d2h(est.data(), d_est, est.size() * 8) ||  fqdev::d2h(sc.data(), d_sex_cnt, sc.size() * 4) || fqdev::d2h(first.data(), d_sex_first, first.size() * 8) || fqdev::sync() ||
-      fqdev::dzero(d_depth, (T + 1) * 4) || fqdev::dzero(d_q20, (T + 1) * 4) || fqdev::dzero(d_q30, (T + 1) * 4) || fqdev::dzero(d_hist, hist.size() * 8) || fqdev::dzero(d_insert, ins.size() * 8) || fqdev::dzero(d_est, est.size() * 8) ||
-      fqdev::dzero(d_sex_cnt, sc.size() * 4) || fqdev::dfill(d_sex_first, 0xff, first.size() * 8) || fqdev::sync()) {
+  const size_t T = table_size;
+  Sums s;
+  s.zero(T, n_contigs);
+  if (fqdev::d2h(s.depth.data(), d_depth, (T + 1) * 4) || fqdev::d2h(s.q20.data(), d_q20, (T + 1) * 4) || fqdev::d2h(s.q30.data(), d_q30, (T + 1) * 4) || fqdev::d2h(s.hist.data(), d_hist, s.hist.size() * 8) ||
+      fqdev::d2h(s.insert.data(), d_insert, s.insert.size() * 8) || fqdev::d2h(s.est.data(), d_est, s.est.size() * 8) ||  fqdev::d2h(s.sex_cnt.data(), d_sex_cnt, s.sex_cnt.size() * 4) || fqdev::d2h(s.sex_first.data(), d_sex_first, s.sex_first.size() * 8) || fqdev::sync() ||
+      fqdev::dzero(d_depth, (T + 1) * 4) || fqdev::dzero(d_q20, (T + 1) * 4) || fqdev::dzero(d_q30, (T + 1) * 4) || fqdev::dzero(d_hist, s.hist.size() * 8) || fqdev::dzero(d_insert, s.insert.size() * 8) || fqdev::dzero(d_est, s.est.size() * 8) ||
+      fqdev::dzero(d_sex_cnt, s.sex_cnt.size() * 4) || fqdev::dfill(d_sex_first, 0xff, s.sex_first.size() * 8) || fqdev::sync()) {
     err = std::string("QC consumer: reading its tables back failed: ") + fqdev::last_error();
     return FQ_ENODEV;
   }
-  {   // the device keeps the depth as a difference table and, for Q20 / Q30, the bases BELOW the threshold per position (fq_qc_base_record): a running sum gives the
+  fold(s);
+  return FQ_OK;
+}
+// The table forms of fq_emit.h's routines turned into the consumer's tables.
+void fq_qc::fold(const Sums &s) {
+  {   // the depth is kept as a difference table and, for Q20 / Q30, as the bases BELOW the threshold per position (fq_qc_base_record): a running sum gives the
       // depth, the depth less those the quality depths
     uint32_t sd = 0;
-    for (size_t k = 0; k < T; ++k) { sd += d[k]; depth[k] += sd; q20[k] += sd - a[k]; q30[k] += sd - b[k]; }
+    for (size_t k = 0; k < table_size; ++k) { sd += s.depth[k]; depth[k] += sd; q20[k] += sd - s.q20[k]; q30[k] += sd - s.q30[k]; }
   }
-  for (int v = 0; v < 256; ++v) { EmpRep[v] += hist[v]; misEmpRep[v] += hist[256 + v]; EmpCycle[v] += hist[512 + v]; misEmpCycle[v] += hist[768 + v]; }
-  for (int v = 0; v < kInsertLimit; ++v) InsertDist[v] += ins[v];
-  for (size_t v = 0; v < est.size(); ++v) est_hist[v] += est[v];
+  for (int v = 0; v < 256; ++v) { EmpRep[v] += s.hist[v]; misEmpRep[v] += s.hist[256 + v]; EmpCycle[v] += s.hist[512 + v]; misEmpCycle[v] += s.hist[768 + v]; }
+  for (int v = 0; v < kInsertLimit; ++v) InsertDist[v] += s.insert[v];
+  for (size_t v = 0; v < s.est.size(); ++v) est_hist[v] += s.est[v];
   std::vector<std::pair<uint64_t, size_t>> order;     // sex-chromosome contigs in the order of their first count
-  for (size_t c = 0; c < nc; ++c) if (first[c] != ~0ull) order.emplace_back(first[c], c);
+  for (size_t c = 0; c < n_contigs; ++c) if (s.sex_first[c] != ~0ull) order.emplace_back(s.sex_first[c], c);
   std::sort(order.begin(), order.end());
   for (const auto &oc : order) {
     ContigStatus &st = cs(ix->contigs[oc.second].name);
-    st.overlapped += (int)sc[oc.second * 4]; st.fully += (int)sc[oc.second * 4 + 1]; st.pair_overlapped += (int)sc[oc.second * 4 + 2]; st.fully_paired += (int)sc[oc.second * 4 + 3];
+    const uint32_t *sc = &s.sex_cnt[oc.second * 4];
+    st.overlapped += (int)sc[0]; st.fully += (int)sc[1]; st.pair_overlapped += (int)sc[2]; st.fully_paired += (int)sc[3];
   }
-  return FQ_OK;
+}
+// The duplicate keys a call listed (outer ends of its proper pairs, ~0: none), in pair order, as the reference spells them: "%d:%d:%d" of contig and both ends
+// (ProcessPairStatus, :905-916).  A shard consumer logs them for the merge.  count_repeats: they are looked up in this consumer's own set here (the host
+// loop; the kernels look theirs up in the set on the device, and list them only for a shard consumer, whose repeats the merge counts).
+void fq_qc::take_keys(const uint64_t *keys, int n_surv, bool count_repeats) {
+  char key[64];
+  for (int sp = 0; sp < n_surv; ++sp) {
+    const uint64_t k = keys[sp];
+    if (k == FQ_QC_DUP_EMPTY) continue;
+    int contig = 0;
+    fq_coor_pac2real(ix, (int64_t)(k >> 32), 1, &contig);      // (a proper pair's outer ends lie inside its contig)
+    snprintf(key, sizeof key, "%d:%d:%d", contig, (int)(uint32_t)(k >> 32), (int)(uint32_t)k);
+    if (count_repeats && !dup_table.insert(key).second) NumPCRDup += 2;
+    if (shard) dup_log.emplace_back(key);
+  }
+}
+
+// ---- the host loop ------------------------------------------------------------------------------------------------------------------
+// fq_emit.h's statement over a call whose arrays are in host memory (a.s: fq_ctx_host_view), in the steps the kernels take (fq_align.cpp: emit_measure, emit_fill):
+// the pairs' decisions in input order on one thread, the prefix sums that place lines and pileup entries, then per record -- over ranges of pairs on threads of
+// their own -- the line, the pileup entries and the per-base sums (depth tables shared and added to atomically, quality / cycle histograms per thread).  The
+// duplicate keys are always listed, and this consumer's set looks them up in pair order.
+void fq_qc::host_call(FqQcArgs &a) {
+  const int P = a.s.n_surv;
+  const size_t N = 2 * (size_t)P;
+  Sums &s = host_sums;
+  if (s.depth.empty()) s.zero(table_size, n_contigs);
+  a.ix.pac = ix->pac.data(); a.ix.l_pac = ix->l_pac;
+  a.g = geom_through([](const auto &v) { return v.data(); });
+  a.cal_dup = o.cal_dup; a.list_keys = 1;
+  a.ord_base = ord_next;
+  ord_next += (uint64_t)P;
+  a.depth = s.depth.data(); a.q20 = s.q20.data(); a.q30 = s.q30.data(); a.hist = s.hist.data(); a.insert_dist = s.insert.data();
+  a.sex_cnt = s.sex_cnt.data(); a.sex_first = s.sex_first.data(); a.est_hist = s.est.data();
+  uint64_t cnt[FQ_QC_C_COUNT] = {};
+  std::vector<int32_t> added(N + 1);
+  std::vector<uint32_t> ist_len((size_t)P + 1), pt_cnt(N + 1);
+  std::vector<uint64_t> ist_off((size_t)P + 1), pt_off(N + 1), keys((size_t)P + 1);
+  a.counters = cnt; a.dup_key = keys.data(); a.added = added.data();
+  a.ist_len = ist_len.data(); a.ist_off = ist_off.data(); a.pt_cnt = pt_cnt.data(); a.pt_off = pt_off.data();
+  for (int sp = 0; sp < P; ++sp) fq_qc_pair_thread(a, sp);
+  for (int sp = 0; sp < P; ++sp) ist_off[(size_t)sp + 1] = ist_off[sp] + ist_len[sp];
+  for (size_t i = 0; i < N; ++i) pt_off[i + 1] = pt_off[i] + pt_cnt[i];
+  std::vector<char> text(ist_off[P]);
+  std::vector<FqPileEntry> pt(pt_off[N]);
+  a.ist_text = text.data(); a.pt = pt.data();
+  std::vector<uint32_t> hist((size_t)FQ_HOST_RANGES * 4 * 256, 0);
+  fq_host_ranges(P, [&](int t, int lo, int hi) {
+    for (int idx = lo; idx < hi; ++idx) {
+      if (!(idx & 1)) fq_qc_ist_fill_thread(a, idx >> 1);
+      fq_qc_pile_fill_thread(a, idx);
+      fq_qc_base_record(a, idx, 0, 1, &hist[(size_t)t * 4 * 256]);
+    }
+  });
+  for (size_t b = 0; b < hist.size(); ++b) s.hist[b % (4 * 256)] += hist[b];
+  take_lines(text.data(), text.size());
+  take_piles(pt.data(), pt.size());
+  take_keys(keys.data(), P, true);
+  add_counts(cnt);
 }
 
 // ---- C ABI ------------------------------------------------------------------------------------------------------------------
@@ -746,32 +526,10 @@ extern "C" int fq_qc_end_file(fq_qc_t *q) {
   return FQ_OK;
 }
 
-// AddAlignment(p, 0), :950-1000 with q == nullptr
-int fq_qc::add_alignment_se(Rec &P, const FqHostReads &hb, long long &failed) {
-  int seqid = 0;
-  if (P.type != FQ_TYPE_NO_MATCH) {
-    const int j = (int)(P.end() - P.r->pos);
-    fq_coor_pac2real(ix, P.r->pos, j, &seqid);
-    if ((int64_t)P.r->pos + j - ix->contigs[seqid].offset > ix->contigs[seqid].len) P.type = FQ_TYPE_NO_MATCH;
-  }
-  if (P.type == FQ_TYPE_NO_MATCH) { failed += 2; return 0; }
-  auto partial = [](const Rec &R) { for (uint16_t g : R.r->cigar) if ((g >> 14) == FQ_OP_S) return true; return false; };
-  const std::string pname = contig_name(seqid);
-  if (add_single(P, hb)) {
-    if (pname.find('Y') != std::string::npos || pname.find('X') != std::string::npos) { ++cs(pname).overlapped; if (!partial(P)) ++cs(pname).fully; }
-    pair_status(&P, nullptr, 0);
-    failed += 1;
-    return 1;
-  }
-  failed += 2;
-  return 0;
-}
-
 // the consumer loop of PairEndMapper over one batch (src/BwtMapper.cpp:2026-2052): counters, then AddAlignment per surviving pair
 extern "C" int fq_qc_add_last(fq_qc_t *q, fq_ctx_t *c) {
   if (!q || !c || !q->file_open) return FQ_EINVAL;
   const FqBatchState *S = fq_ctx_state(c);
-  const FqHostReads hb = fq_ctx_host_reads(c);
   const fq_opts_t *ao = fq_ctx_opts(c);
   q->o.mode = ao->mode;
   FileStat &F = q->cur;
@@ -783,69 +541,24 @@ extern "C" int fq_qc_add_last(fq_qc_t *q, fq_ctx_t *c) {
     // records came back laid out in input order and is appended here
     if (D->owner != q || !D->ready) { q->err = "fq_qc_add_last: the context's last call counted for another consumer, or failed"; return FQ_EINVAL; }
     if (fq_ctx_emit_wait(c)) { q->err = std::string("fq_qc_add_last: ") + fq_ctx_last_error(c); return FQ_ENODEV; }      // (the call only enqueued its kernels)
-    F.BwaUnmapped += (long long)D->cnt[FQ_QC_C_UNMAPPED];
-    F.TotalRetained += (long long)(D->cnt[FQ_QC_C_RETAINED1] + 2 * D->cnt[FQ_QC_C_RETAINED2]);
-    F.TotalMAPQ += (long long)(D->cnt[FQ_QC_C_FAILED1] + 2 * D->cnt[FQ_QC_C_FAILED2]);
-    q->NumPairReads += 2 * D->cnt[FQ_QC_C_PROPER];
-    q->NumPCRDup += 2 * D->cnt[FQ_QC_C_DUP];
-    if (D->ist_bytes && fq_ctx_qc_stream(c, 0, [](void *user, const void *data, int64_t n) -> int { ((fq_qc *)user)->table.write((const char *)data, (std::streamsize)n); return 0; }, q) < 0) {
+    q->add_counts(D->cnt);
+    if (D->ist_bytes && fq_ctx_qc_stream(c, 0, [](void *user, const void *data, int64_t n) -> int { ((fq_qc *)user)->take_lines((const char *)data, (size_t)n); return 0; }, q) < 0) {
       q->err = std::string("fq_qc_add_last: fetching the .InsertSizeTable lines failed: ") + fq_ctx_last_error(c);
       return FQ_ENODEV;
     }
-    if (D->n_pile && fq_ctx_qc_stream(c, 1, [](void *user, const void *data, int64_t n) -> int {
-          fq_qc *Q = (fq_qc *)user;
-          const FqPileEntry *e = (const FqPileEntry *)data;
-          for (int64_t t = 0; t < n / (int64_t)sizeof(FqPileEntry); ++t, ++e) {
-            Q->seq_vec[e->k] += (char)e->base; Q->qual_vec[e->k] += (char)e->qual;
-            Q->cycle_vec[e->k].push_back(e->cyc); Q->maq_vec[e->k].push_back(e->maq); Q->strand_vec[e->k].push_back(e->strand != 0);
-          }
-          return 0;
-        }, q) < 0) {
+    if (D->n_pile && fq_ctx_qc_stream(c, 1, [](void *user, const void *data, int64_t n) -> int { ((fq_qc *)user)->take_piles((const FqPileEntry *)data, (size_t)n / sizeof(FqPileEntry)); return 0; }, q) < 0) {
       q->err = std::string("fq_qc_add_last: fetching the pileup entries failed: ") + fq_ctx_last_error(c);
       return FQ_ENODEV;
     }
-    if (q->shard && D->dup_key) {
-      char key[64];
-      for (int sp = 0; sp < D->n_surv; ++sp) {
-        const uint64_t k = D->dup_key[sp];
-        if (k == FQ_QC_DUP_EMPTY) continue;
-        int contig = 0;
-        fq_coor_pac2real(q->ix, (int64_t)(k >> 32), 1, &contig);      // (a proper pair's outer ends lie inside its contig)
-        snprintf(key, sizeof key, "%d:%d:%d", contig, (int)(uint32_t)(k >> 32), (int)(uint32_t)k);
-        q->dup_log.emplace_back(key);
-      }
-    }
+    if (q->shard && D->dup_key) q->take_keys(D->dup_key, D->n_surv, false);
     return FQ_OK;
   }
   if (q->device_adds) { q->err = "fq_qc_add_last: this consumer counts on the device (fq_ctx_attach_qc); a batch of a context without it cannot be mixed in"; return FQ_EINVAL; }
   q->host_adds = true;
   q->est_valid = false;
-  if (S->n_surv > 0 && !S->rec) { q->err = "fq_qc_add_last: the call's result arrays were left on the device (FQ_EMIT_DEVICE_ONLY)"; return FQ_EINVAL; }
-  if (S->n_surv > 0 && !hb.has_qual()) { q->err = "the batch carries no qualities"; return FQ_EINVAL; }
-  // the batch's records in the host's vocabulary, from the C-ABI arrays (all threads); they live until the per-base statistics have run
-  std::vector<FqRead> recs((size_t)S->n_surv * 2);
-  {
-    const size_t n = recs.size();
-    const int T = n >= 4096 ? 8 : 1;
-    const size_t per = (n + (size_t)T - 1) / (size_t)T;
-    auto fill = [&](int t) { const size_t lo = (size_t)t * per, hi = std::min(n, lo + per); for (size_t i = lo; i < hi; ++i) recs[i] = S->read(i); };
-    if (T == 1) fill(0); else q->pool.run(T, fill);
-  }
-  for (int sp = 0; sp < S->n_surv; ++sp) {
-    const FqRead &a = recs[2 * (size_t)sp], &b = recs[2 * (size_t)sp + 1];
-    if (a.type == FQ_TYPE_NO_MATCH && b.type == FQ_TYPE_NO_MATCH) { ++F.BwaUnmapped; continue; }
-    if (ao->single_end) {   // SingleEndMapper's consumer loop, src/BwtMapper.cpp:1355-1370
-      Rec P;
-      P.r = &a; P.type = a.type; P.name = fq_read_name(&hb, a.r % S->n_pairs, a.r / S->n_pairs, a.revived);
-      F.TotalRetained += q->add_alignment_se(P, hb, F.TotalMAPQ);
-      continue;
-    }
-    Rec P, Q;
-    P.r = &a; P.type = a.type; P.name = fq_read_name(&hb, a.r % S->n_pairs, a.r / S->n_pairs, a.revived);
-    Q.r = &b; Q.type = b.type; Q.name = fq_read_name(&hb, b.r % S->n_pairs, b.r / S->n_pairs, b.revived);
-    F.TotalRetained += q->add_alignment(P, Q, hb, F.TotalMAPQ);
-  }
-  q->run_stat_jobs(hb, 8);
+  FqQcArgs a{};
+  if (const int rc = fq_ctx_host_view(c, &a.s)) { q->err = std::string("fq_qc_add_last: ") + fq_ctx_last_error(c); return rc; }      // (result arrays left on the device, no qualities)
+  q->host_call(a);
   return FQ_OK;
 }
 

@@ -54,18 +54,6 @@ void dump_rec(Out &o, char tag, int end, int idx, const FqRead &p, bool fin) {
 }
 }  // namespace
 
-// fq_emit_name over the two mates' names of the batch (where the second mates carry none of their own both rows hold the same name, and the overlay is the identity)
-std::string fq_read_name(const FqHostReads *hb, int pair, int end, bool revived) {
-  if (!hb->has_names()) return "*";
-  const size_t ns = (size_t)hb->name_stride;
-  std::string two(2 * ns, '\0'), out(ns, '\0');
-  for (int e = 0; e < 2; ++e) { const char *nm = hb->name_of(pair, e); memcpy(&two[(size_t)e * ns], nm, strnlen(nm, ns)); }
-  FqTxt o; o.dst = &out[0]; o.at = 0;
-  fq_emit_name(two.data(), (int)ns, end, revived, o);
-  out.resize((size_t)o.at);
-  return out;
-}
-
 extern "C" int64_t fq_sam_header(const fq_index_t *ix, char *buf, int64_t cap) {
   if (!ix) return FQ_EINVAL;
   Out o;

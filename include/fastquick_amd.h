@@ -421,7 +421,8 @@ int fq_qc_merge(fq_qc_t *q, const void *buf, int64_t len);
  * its pileup entries; prefix sums place them in input order; a wavefront per added read adds its bases to the depth / Q20 / Q30 tables of the
  * flank regions and to the quality / cycle histograms (AddSingleAlignment, :424-620), which stay in HBM until fq_qc_write / fq_qc_state_export
  * fetch them; proper pairs' duplicate keys go into a hash set in HBM (ProcessPairStatus, :623-921).  fq_qc_add_last(q, c) then only appends what
- * came back in input order (lines, pileup entries) and adds the call's counters.  The files are the host path's byte for byte.  A consumer
+ * came back in input order (lines, pileup entries) and adds the call's counters.  Without an attached context fq_qc_add_last runs the same
+ * routines of fq_emit.h in a loop on the host over the result arrays (one statement, two loops): the files are the same either way.  A consumer
  * counts on one side only: every context that feeds it must have it attached (or none); calls of contexts that share a consumer must not
  * overlap.  q = NULL detaches. */
 int fq_ctx_attach_qc(fq_ctx_t *c, fq_qc_t *q);

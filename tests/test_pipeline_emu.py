@@ -228,6 +228,59 @@ def test_host_formatter_reads_every_input_kind(emu_lib, tmp_path):
     assert n == 0 and b"".join(got) == want, "text-resident"
 
 
+def test_host_qc_consumer_reads_every_input_kind(golden_cases, emu_lib, tmp_path):
+    """The host side of the QC consumer loops over fq_emit.h's StatCollector statement on the same host view (fq_ctx_host_view): rows through
+    fq_emit_row and the view's stride, qualities and names compact.  Golden `basic` in batches of 64 pairs as ASCII batches, packed batches and
+    text-resident batches (fq_align_text) must give the same 13 files -- and files that say something."""
+    from fastquick_amd import synth
+    from test_qc_consumer import QC_FILES, qc_bytes
+    g = golden_cases["basic"]
+    B = 64
+    names, seq, qual, lens = ob.read_fastq_pair(g["fq1"], g["fq2"])
+    n = seq.shape[1]
+    ix = api.Index(g["prefix"], lib=emu_lib)
+    kw = dict(genome_size=g["genome_size"], read_len=g["qc_read_len"])
+    okw = dict(trim_qual=g["trim_qual"], batch_pairs=B)
+
+    def consumer(kind):
+        qc = api.QC(ix, g["prefix"], str(tmp_path / kind), **kw)
+        qc.begin_file(g["fq1"], g["fq2"])
+        return qc, api.Aligner(ix, api.default_opts(emu_lib, **okw), max_pairs=B)
+
+    def files(kind, qc, al):
+        qc.end_file(); qc.write(); qc.close(); al.close()
+        return {f: qc_bytes(str(tmp_path / kind) + "." + f) for f in QC_FILES}
+
+    out = {}
+    for kind in ("ascii", "packed"):
+        qc, al = consumer(kind)
+        api.align_stream(al, names, seq, qual, lens, B, None, None, qc=qc, packed=kind == "packed")
+        out[kind] = files(kind, qc, al)
+    fq = []
+    for e in range(2):
+        fq.append(str(tmp_path / ("reads_%d.fq.gz" % (e + 1))))
+        text = b"".join(b"@" + bytes(names[i]) + b"\n" + bytes(seq[e, i, :lens[e, i]]) + b"\n+\n" + bytes(qual[e, i, :lens[e, i]]) + b"\n" for i in range(n))
+        with open(fq[e], "wb") as fh:
+            fh.write(synth.bgzf_compress(text, threads=2, level=6, member=4000))
+    fe = api.DeviceFrontEnd(fq[0], fq[1], batch_pairs=B, chunk_pairs=B, slot_mode=0, max_read_len=int(lens.max()) + 9, lib=emu_lib)
+    qc, al = consumer("text")
+    while True:
+        m, b = fe.next()
+        if m <= 0:
+            break
+        al.align_text(b)
+        qc.add(al)
+        fe.release(b)
+    fe.close()
+    out["text"] = files("text", qc, al)
+    ix.close()
+    assert m == 0
+    assert out["ascii"]["InsertSizeTable"].count(b"\n") > n // 2 and len(out["ascii"]["Pileup"]) > 1000 and b"PropPair" in out["ascii"]["InsertSizeTable"]
+    for kind in ("packed", "text"):
+        bad = [f for f in QC_FILES if out[kind][f] != out["ascii"][f]]
+        assert not bad, "%s batches: %s differ from the ASCII batches' files" % (kind, bad)
+
+
 def trimmed_max_len_case(lib, tmp_path, device=None):
     """infer_isize's max_len is the longest TRIMMED read of the reference batch, filtered reads included (bwape.c:60-61).  Short
     fragments make the estimate's lower bound equal to it (p25 - 2 IQR < max_len), so it shows in the result.  Every on-target
