@@ -106,7 +106,8 @@ EXPORTS = ["fq_default_opts", "fq_index_build", "fq_index_load", "fq_index_destr
            "fq_fastq_open", "fq_fastq_configure", "fq_fastq_set_sampling", "fq_fastq_read", "fq_fastq_last_error", "fq_fastq_dropped_record", "fq_fastq_unequal_lengths", "fq_fastq_is_bgzf", "fq_fastq_close", "fq_inflate_raw", "fq_crc32", "fq_inflate_device", "fq_bgzf_inflate_device",
            "fq_frontend_open", "fq_frontend_next", "fq_frontend_release", "fq_frontend_handover", "fq_frontend_unequal_lengths", "fq_frontend_stats", "fq_frontend_last_error", "fq_frontend_close",
            "fq_text_batch_pairs", "fq_text_batch_first_name", "fq_align_text", "fq_text_batch_fetch",
-           "fq_ctx_set_emit", "fq_sam_device_last", "fq_sam_device_bytes", "fq_ctx_attach_qc", "fq_ctx_attach_bam", "fq_bgzf_deflate_device"]
+           "fq_ctx_set_emit", "fq_sam_device_last", "fq_sam_device_bytes", "fq_ctx_attach_qc", "fq_ctx_attach_bam", "fq_bgzf_deflate_device",
+           "fq_bam_create_sorted", "fq_bam_sort_stats", "fq_bam_sort_stats_at_close", "fq_bam_sort_run_entries", "fq_sort_keys_device"]
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)
 EMIT_SAM = 1
 
@@ -613,20 +614,75 @@ class QC:
             self.h = None
 
 
+class BamSortStats(C.Structure):      # fq_bam_sort_stats_t
+    _fields_ = [("runs", C.c_int64), ("device_sorted_runs", C.c_int64), ("spilled_runs", C.c_int64), ("records", C.c_int64), ("key_bits", C.c_int32), ("pos_bits", C.c_int32),
+                ("sort_kernel_ms", C.c_double), ("gather_kernel_ms", C.c_double), ("close_sec", C.c_double), ("close_sort_sec", C.c_double), ("close_assemble_sec", C.c_double),
+                ("close_compress_sec", C.c_double), ("close_index_sec", C.c_double)]
+
+
 class BamWriter:
     """The BAM consumer (SetSamRecord / SetSamFileHeader): genome-coordinate records of every batch of a stream."""
 
-    def __init__(self, index: Index, fai_path: str, bam_path: str, rg: str = "@RG\\tID:foo\\tSM:bar", **kw):
+    def __init__(self, index: Index, fai_path: str, bam_path: str, rg: str = "@RG\\tID:foo\\tSM:bar", sorted: bool = False, sort_mem: int = 1 << 30, **kw):
+        """sorted=True: bam_path becomes the coordinate-sorted file and bam_path + ".bai" its index (fq_bam_create_sorted); the records are kept as runs,
+        up to sort_mem bytes of them in host memory, and leave at close()."""
         self.L = index.L
+        self.sorted = sorted
+        self._at_close = BamSortStats()
         o = QcOpts()
         self.L.fq_qc_default_opts(C.byref(o))
         for k, v in kw.items():
             setattr(o, k, v)
         h = C.c_void_p()
-        rc = self.L.fq_bam_create(index.h, fai_path.encode(), bam_path.encode(), rg.encode(), C.byref(o), C.byref(h))
+        if sorted:
+            self.L.fq_bam_create_sorted.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(QcOpts), C.c_int64, C.POINTER(C.c_void_p)]
+            rc = self.L.fq_bam_create_sorted(index.h, fai_path.encode(), bam_path.encode() if bam_path else None, rg.encode(), C.byref(o), int(sort_mem), C.byref(h))
+        else:
+            rc = self.L.fq_bam_create(index.h, fai_path.encode(), bam_path.encode() if bam_path else None, rg.encode(), C.byref(o), C.byref(h))      # (no path: a formatter without a file, for format_last())
         if rc:
-            raise FastquickError("fq_bam_create failed: %d" % rc)
+            raise FastquickError("fq_bam_create%s failed: %d" % ("_sorted" if sorted else "", rc))
         self.h = h
+        if sorted:
+            self.L.fq_bam_sort_stats.argtypes = [C.c_void_p, C.POINTER(BamSortStats)]
+            self.L.fq_bam_sort_stats_at_close.argtypes = [C.c_void_p, C.POINTER(BamSortStats)]
+            self.L.fq_bam_sort_stats_at_close(self.h, C.byref(self._at_close))
+
+    def write_records(self, data: bytes):
+        """whole BAM records as bytes (what format_last() of another writer handed out): appended, or one more run of a sorted writer"""
+        self.L.fq_bam_write_records.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
+        rc = self.L.fq_bam_write_records(self.h, data, len(data))
+        if rc:
+            raise FastquickError("fq_bam_write_records failed: %d" % rc)
+
+    def format_last(self, aligner: "Aligner") -> bytes:
+        """the records of the aligner's last batch as bytes, in input order (fq_bam_format_last)"""
+        self.L.fq_bam_format_last.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+        d, n = C.c_void_p(), C.c_int64(0)
+        rc = self.L.fq_bam_format_last(self.h, aligner.h, C.byref(d), C.byref(n))
+        if rc:
+            raise FastquickError("fq_bam_format_last failed: %d" % rc)
+        return C.string_at(d, n.value) if n.value else b""
+
+    def run_entries(self, run: int = -1):
+        """the sort entries of a run of a sorted writer (run < 0: from the last): a structured array of key, len, end in the order the run holds its records"""
+        dt = np.dtype([("key", "<u8"), ("len", "<u4"), ("end", "<i4")])
+        self.L.fq_bam_sort_run_entries.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
+        self.L.fq_bam_sort_run_entries.restype = C.c_int64
+        n = self.L.fq_bam_sort_run_entries(self.h, run, None, 0)
+        if n < 0:
+            raise FastquickError("fq_bam_sort_run_entries failed: %d" % n)
+        out = np.zeros(max(1, n), dtype=dt)
+        self.L.fq_bam_sort_run_entries(self.h, run, out.ctypes.data, n)
+        return out[:n]
+
+    def sort_stats(self) -> dict:
+        """a sorted writer's runs and times (fq_bam_sort_stats); after close() the figures the close left, its seconds included"""
+        st = self._at_close
+        if self.h:
+            st = BamSortStats()
+            if self.L.fq_bam_sort_stats(self.h, C.byref(st)):
+                raise FastquickError("fq_bam_sort_stats: not a sorted writer")
+        return {k: getattr(st, k) for k, _ in BamSortStats._fields_}
 
     def attach(self, aligner: "Aligner"):
         """the records of every later call of `aligner` are formatted by the kernels of fq_emit.h inside the call (fq_ctx_attach_bam); add() fetches the bytes"""
@@ -721,6 +777,19 @@ def bgzf_deflate_device(data: bytes, device: int = 0, lib=None):
     if rc:
         raise FastquickError("fq_bgzf_deflate_device failed: %d" % rc)
     return out[:ol.value].tobytes(), ms.value
+
+
+def sort_keys_device(keys, key_bits: int, device: int = 0, lib=None):
+    """the stable ascending order of 64-bit keys by the device's radix sort (fq_sort.h): (perm, kernel_ms), perm[i] = the place in keys of the i-th key"""
+    L = lib or load_library()
+    k = np.ascontiguousarray(keys, dtype=np.uint64)
+    perm = np.empty(max(1, k.size), dtype=np.uint32)
+    ms = C.c_double(0)
+    L.fq_sort_keys_device.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+    rc = L.fq_sort_keys_device(device, k.ctypes.data if k.size else None, k.size, key_bits, perm.ctypes.data, C.byref(ms))
+    if rc:
+        raise FastquickError("fq_sort_keys_device failed: %d" % rc)
+    return perm[:k.size], ms.value
 
 
 def bgzf_inflate_device(blob: bytes, text_cap: int, device: int = 0, lib=None, repeats: int = 1):

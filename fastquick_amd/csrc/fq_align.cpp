@@ -358,6 +358,10 @@ struct fq_ctx {
   fq_bam *bam = nullptr;
   DevBuf<uint32_t> d_bamlen, d_bammeta, d_zsize; DevBuf<uint64_t> d_bamoff, d_zoff; DevBuf<uint8_t> d_bamrec, d_zstage, d_bamz;
   FqBamCallOut bam_out;
+  double idle_ms[FQ_K_COUNT] = {}; uint64_t idle_launches[FQ_K_COUNT] = {};      // kernel times collected between calls (fq_ctx_emit_wait), folded into stats by the next call
+  double sort_ms_total = 0, gather_ms_total = 0, sort_ms_given = 0, gather_ms_given = 0;      // FQ_KX_SORT / FQ_KX_GATHER over the context's calls; what the runs handed to the writer have taken of it
+  // ... and, for a sorted writer, the same records in key order (fq_sort.h): entries, keys, the sort's ping-pong buffers, the gathered records
+  DevBuf<FqBamSortEnt> d_sortent, d_sortent2; DevBuf<uint64_t> d_sortkey, d_sortkey2, d_sortkey3, d_sorthoff, d_sortoff; DevBuf<uint32_t> d_sortperm, d_sortperm2, d_sorthist, d_sortlen; DevBuf<uint8_t> d_bamrec2;
   PinBuf<uint64_t> p_ztotal;
   uint32_t emit_nb = 0;
   std::mutex emit_mu;                  // the fill kernels of the last call may still run (emit_pending): the first fetcher waits for them
@@ -2119,6 +2123,18 @@ int emit_args(Call &K, FqSamArgs &a) {
   a = K.emit;
   return FQ_OK;
 }
+// the finished kernels' times into the context's statistics (on the bound state); a sorted writer's sort and gather kernels count among the consumers' kernels, and apart
+static void collect_kernel_times(fq_ctx *c, bool in_call) {
+  // Between two calls (fq_ctx_emit_wait, possibly on a writer's thread) the times only gather in fields of their own, under emit_mu; the call that follows folds them into
+  // the context's statistics on the calling thread, the only one that writes those.
+  double ms[FQ_KX_COUNT] = {0}; uint64_t ln[FQ_KX_COUNT] = {0};
+  fqdev::time_collect(ms, ln, FQ_KX_COUNT);
+  ms[FQ_K_EMIT] += ms[FQ_KX_SORT] + ms[FQ_KX_GATHER]; ln[FQ_K_EMIT] += ln[FQ_KX_SORT] + ln[FQ_KX_GATHER];
+  for (int k = 0; k < FQ_K_COUNT; ++k) { c->idle_ms[k] += ms[k]; c->idle_launches[k] += ln[k]; }
+  c->sort_ms_total += ms[FQ_KX_SORT]; c->gather_ms_total += ms[FQ_KX_GATHER];
+  if (!in_call) return;
+  for (int k = 0; k < FQ_K_COUNT; ++k) { c->stats.kernel_ms[k] += c->idle_ms[k]; c->stats.kernel_launches[k] += c->idle_launches[k]; c->idle_ms[k] = 0; c->idle_launches[k] = 0; }
+}
 // The consumers' kernels run in two steps.  emit_measure, inside the call: every record's line / record length and every pair's decisions, the prefix
 // sums that place them, ONE wait for the totals.  emit_fill, as the call's last act: the buffers, then the kernels that write -- SAM text, BAM records
 // and their BGZF members, .InsertSizeTable lines, pileup entries, the per-base sums -- are only ENQUEUED: the call returns, and they run beside the next
@@ -2200,6 +2216,24 @@ int emit_fill(Call &K) {
     CK(fqdev::launch_bam(FQ_EOP_BAM_BODY, E.bam, (int64_t)N));      // packed bases and qualities: a thread per sixteen bytes
     c->bam_out.bytes = total;
     c->emit_nb = 0;
+    int sort_n_ref = 0, sort_pos_bits = 0, sort_key_bits = 0;
+    if (fq_bam_sort_params(c->bam, &sort_n_ref, &sort_pos_bits, &sort_key_bits)) {
+      // a sorted writer: the call's records leave as a run in key order -- entries, the stable sort of their keys, the entries permuted along and their
+      // lengths scanned, the records gathered into a second buffer.  No members here: the writer compresses once, behind its merge.
+      const uint32_t n = (uint32_t)N;
+      const size_t nh = (size_t)FQ_SORT_DIGITS * fq_sort_tiles(n);
+      CKM(c->d_sortent.ensure(N + 1) && c->d_sortent2.ensure(N + 1) && c->d_sortkey.ensure(N + 1) && c->d_sortkey2.ensure(N + 1) && c->d_sortkey3.ensure(N + 1) && c->d_sortperm.ensure(N + 1) &&
+          c->d_sortperm2.ensure(N + 1) && c->d_sorthist.ensure(nh + 1) && c->d_sorthoff.ensure(nh + 2) && c->d_sortlen.ensure(N + 1) && c->d_sortoff.ensure(N + 2) && c->d_bamrec2.ensure_roomy(total + 64));
+      const FqBamKeyArgs ka{c->d_bamrec.p, c->d_bamoff.p, c->d_bamlen.p, c->d_sortent.p, c->d_sortkey.p, n, sort_n_ref, sort_pos_bits};
+      CK(fqdev::launch_bam_key(ka));
+      const FqSortScratch sc{c->d_sortkey3.p, c->d_sortperm2.p, c->d_sorthist.p, c->d_sorthoff.p};
+      CK(fqdev::launch_sort_pairs(c->d_sortkey.p, n, sort_key_bits, c->d_sortkey2.p, c->d_sortperm.p, sc));
+      CK(fqdev::launch_sort_permute(c->d_sortent.p, c->d_sortperm.p, n, c->d_sortent2.p, c->d_sortlen.p));
+      CK(fqdev::launch_scan(c->d_sortlen.p, c->d_sortoff.p, n));
+      const FqBamGatherArgs ga{c->d_bamrec.p, c->d_bamoff.p, c->d_sortperm.p, c->d_sortoff.p, c->d_bamrec2.p, n, total};
+      CK(fqdev::launch_bam_gather(ga));
+      c->bam_out.sorted = true; c->bam_out.n_rec = N;
+    }
     if (total && fq_bam_wants_members(c->bam)) {
       // the writer has a file: the records leave the device as finished BGZF members (fq_deflate.h: a wavefront per block of the record stream),
       // packed behind each other into a buffer sized for the worst case; their size comes back with the wait
@@ -2311,7 +2345,7 @@ int stage_finish(Call &K, fq_result_batch_t *out) {
   out->n_sub = n_sub;
   out->isize_sub = S.isize_sub.data();
   out->n_bases = c->n_bases_in;
-  fqdev::time_collect(c->stats.kernel_ms, c->stats.kernel_launches, FQ_K_COUNT);
+  { std::lock_guard<std::mutex> lk(c->emit_mu); collect_kernel_times(c, true); }
   c->stats.occ_block_touches += cnt[FQ_C_OCC_WIDTH] + cnt[FQ_C_OCC_GAP] + cnt[FQ_C_OCC_SA];
   c->stats.gap_occ_touches += cnt[FQ_C_OCC_GAP];
   c->stats.width_occ_touches += cnt[FQ_C_OCC_WIDTH];
@@ -2686,6 +2720,11 @@ int fq_ctx_emit_wait(fq_ctx_t *c) {
   if (c->qc && c->qc_out.ready)
     for (int k = 0; k < FQ_QC_C_COUNT; ++k) { uint64_t v = 0; for (int st = 0; st < FQ_C_STRIPES; ++st) v += c->p_qcnt.p[(size_t)st * FQ_C_STRIDE + k]; c->qc_out.cnt[k] = v; }
   if (c->bam && c->emit_nb) c->bam_out.z_bytes = c->p_ztotal.p[0];
+  if (c->bam_out.sorted) {      // what the run's sort and gather kernels took (events of earlier runs that were still open then land here)
+    collect_kernel_times(c, false);
+    c->bam_out.sort_ms = c->sort_ms_total - c->sort_ms_given; c->bam_out.gather_ms = c->gather_ms_total - c->gather_ms_given;
+    c->sort_ms_given = c->sort_ms_total; c->gather_ms_given = c->gather_ms_total;
+  }
   c->emit_pending = false;
   return FQ_OK;
 }
@@ -2714,10 +2753,15 @@ extern "C" int64_t fq_sam_device_last(fq_ctx_t *c, fq_sink_fn sink, void *user) 
   return stream_device_bytes(c, 0, c->d_samtext.p, c->sam_bytes, sink, user, "fq_sam_device_last");
 }
 // the BAM records of the last call (fq_ctx_attach_bam), for the writer they were formatted for
-int64_t fq_ctx_bam_stream(fq_ctx_t *c, fq_sink_fn sink, void *user, int members) {
+int64_t fq_ctx_bam_stream(fq_ctx_t *c, fq_sink_fn sink, void *user, int what) {
   if (!c->bam || !c->bam_out.ready) { c->err = "the last call formatted no BAM records on the device"; return FQ_EINVAL; }
   if (fq_ctx_emit_wait(c)) return FQ_ENODEV;
-  if (members) return stream_device_bytes(c, 0, (const char *)c->d_bamz.p, c->bam_out.z_bytes, sink, user, "BGZF members");
+  if (what == FQ_BAM_STREAM_SORTED || what == FQ_BAM_STREAM_ENTRIES) {
+    if (!c->bam_out.sorted) { c->err = "the last call did not sort its BAM records on the device"; return FQ_EINVAL; }
+    if (what == FQ_BAM_STREAM_SORTED) return stream_device_bytes(c, 0, (const char *)c->d_bamrec2.p, c->bam_out.bytes, sink, user, "sorted BAM records");
+    return stream_device_bytes(c, 0, (const char *)c->d_sortent2.p, c->bam_out.n_rec * sizeof(FqBamSortEnt), sink, user, "sort entries", sizeof(FqBamSortEnt));
+  }
+  if (what == FQ_BAM_STREAM_MEMBERS) return stream_device_bytes(c, 0, (const char *)c->d_bamz.p, c->bam_out.z_bytes, sink, user, "BGZF members");
   return stream_device_bytes(c, 0, (const char *)c->d_bamrec.p, c->bam_out.bytes, sink, user, "BAM records");
 }
 extern "C" int fq_ctx_attach_bam(fq_ctx_t *c, fq_bam_t *b) {

@@ -7,6 +7,7 @@
 #include "fq_frontend.h"
 #include "fq_emit.h"
 #include "fq_deflate.h"
+#include "fq_sort.h"
 
 namespace fqdev {
 

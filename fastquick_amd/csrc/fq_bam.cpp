@@ -4,12 +4,22 @@
 // CHR:POS@REF/ALT[|L], the record's RNAME is CHR and its position POS - flank + offset-in-contig - 1 (:1026-1043), the header's
 // @SQ lines are the original reference's (.fai), and every record carries RG:Z.  The record itself is fq_emit.h's fq_bam_record, the
 // routine the consumers' kernels run: the host formatter loops over it on the host's view of the call (fq_ctx_host_view).
+// fq_bam_create_sorted: the same records as a coordinate-sorted file with its .bai (what the pipeline's samtools sort / index steps make of O.bam, bin/FASTQuick_template.sh:501-502).
+// The records are kept as runs until the close, which sorts all keys on the device (fq_sort.h) and emits in that order.  Runs that a call sorted on the device are read front
+// to back by the emission; runs handed over as bytes (host formatter, fq_bam_write_records, the part files of --devices) are read at random -- fine in memory, slow from a
+// spill file (a pread per record).
+#include <fcntl.h>
+#include <unistd.h>
 #include <zlib.h>
 
+#include <algorithm>
+#include <atomic>
+#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
 #include <map>
+#include <memory>
 #include <sstream>
 #include <string>
 #include <thread>
@@ -99,9 +109,35 @@ struct Bgzf {
   }
 };
 
+// ---- the sorted writer's runs (fq_bam_create_sorted) -------------------------------------------------------------------------
+// One run per fq_bam_add_last / fq_bam_write_records: the record bytes and one FqBamSortEnt per record (fq_sort.h).  A run an attached context sorted on
+// the device arrives in key order with its entries and is read front to back by the emission; a run handed over as bytes stays in input order, its
+// entries come from the host loop over fq_bam_sort_entry, and the emission reads it at random -- fine in memory, slow from a spill file (a pread per record).
+struct SortRun {
+  std::vector<uint8_t> bytes;            // (empty when the run went to a file)
+  std::vector<FqBamSortEnt> ent;
+  std::vector<uint64_t> off;             // made at close: where each record begins in the run
+  uint64_t n_bytes = 0;
+  bool device_sorted = false;
+  int fd = -1;
+  std::string path;
+};
+struct SortWriter {
+  std::string path;
+  uint64_t mem_limit = 0, mem_used = 0, records = 0;
+  int n_ref = 0, pos_bits = 1, key_bits = 2, n_tmp = 0;
+  std::vector<SortRun> runs;
+  fq_bam_sort_stats_t st{};
+  fq_bam_sort_stats_t *at_close = nullptr;
+  ~SortWriter() { for (SortRun &r : runs) { if (r.fd >= 0) ::close(r.fd); if (!r.path.empty()) ::unlink(r.path.c_str()); } }      // (also after a failed close)
+};
+static int bit_length(uint64_t v) { int b = 0; while (v) { ++b; v >>= 1; } return b; }
+static double now_sec() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
 }  // namespace
 
 struct fq_bam {
+  std::unique_ptr<SortWriter> sort;      // fq_bam_create_sorted: the records are kept as runs and leave at close
   // the formatter's tables (fq_emit.h: FqBamArgs): per contig the BAM reference id of its chromosome and where it lies in the genome;
   // made with the writer, uploaded when the first call formats on the device
   std::vector<int32_t> ctg_rid, ctg_g0;
@@ -131,8 +167,8 @@ struct fq_bam {
   int id_of(const std::string &chrom) const { auto it = ref_id.find(chrom); return it == ref_id.end() ? -1 : it->second; }
 };
 
-extern "C" int fq_bam_create(const fq_index_t *ix, const char *fai_path, const char *bam_path, const char *rg_line, const fq_qc_opts_t *o, fq_bam_t **out) {
-  if (!ix || !fai_path || !o || !out) return FQ_EINVAL;
+static int bam_create(const fq_index_t *ix, const char *fai_path, const char *bam_path, const char *rg_line, const fq_qc_opts_t *o, bool sorted, int64_t sort_mem, fq_bam_t **out) {
+  if (!ix || !fai_path || !o || !out || (sorted && (!bam_path || sort_mem < 0))) return FQ_EINVAL;
   *out = nullptr;
   fq_bam *b = new fq_bam;
   b->ix = ix; b->o = *o;
@@ -179,6 +215,17 @@ extern "C" int fq_bam_create(const fq_index_t *ix, const char *fai_path, const c
   if (!bam_path) { *out = b; return FQ_OK; }          // a formatter without a file (fq_bam_format_last)
   b->z.fp = fopen(bam_path, "wb");
   if (!b->z.fp) { delete b; return FQ_EIO; }
+  if (sorted) {
+    b->header_text = "@HD\tVN:1.6\tSO:coordinate\n" + b->header_text;
+    b->sort.reset(new SortWriter);
+    SortWriter &S = *b->sort;
+    S.path = bam_path; S.mem_limit = (uint64_t)sort_mem; S.n_ref = (int)b->contigs.size();
+    int max_ln = 0;
+    for (const auto &cg : b->contigs) max_ln = std::max(max_ln, cg.second);
+    S.pos_bits = std::max(1, bit_length((uint64_t)max_ln + 1));      // room for max LN + 1 and for n_ref: the key's width needs no reduction on the device
+    S.key_bits = std::max(1, bit_length((uint64_t)S.n_ref)) + S.pos_bits + 1;
+    S.st.key_bits = S.key_bits; S.st.pos_bits = S.pos_bits;
+  }
   const int32_t l_text = (int32_t)b->header_text.size(), n_ref = (int32_t)b->contigs.size();
   b->z.write("BAM\1", 4);
   b->z.write(&l_text, 4);
@@ -193,8 +240,19 @@ extern "C" int fq_bam_create(const fq_index_t *ix, const char *fai_path, const c
   *out = b;
   return FQ_OK;
 }
+extern "C" int fq_bam_create(const fq_index_t *ix, const char *fai_path, const char *bam_path, const char *rg_line, const fq_qc_opts_t *o, fq_bam_t **out) {
+  return bam_create(ix, fai_path, bam_path, rg_line, o, false, 0, out);
+}
+extern "C" int fq_bam_create_sorted(const fq_index_t *ix, const char *fai_path, const char *bam_path, const char *rg_line, const fq_qc_opts_t *o, int64_t sort_mem_bytes, fq_bam_t **out) {
+  return bam_create(ix, fai_path, bam_path, rg_line, o, true, sort_mem_bytes, out);
+}
 
-bool fq_bam_wants_members(const fq_bam *b) { return b->z.fp != nullptr && !b->host_deflate; }
+bool fq_bam_sort_params(const fq_bam *b, int *n_ref, int *pos_bits, int *key_bits) {
+  if (!b || !b->sort) return false;
+  *n_ref = b->sort->n_ref; *pos_bits = b->sort->pos_bits; *key_bits = b->sort->key_bits;
+  return true;
+}
+bool fq_bam_wants_members(const fq_bam *b) { return b->z.fp != nullptr && !b->host_deflate && !b->sort; }      // (a sorted writer compresses once, behind the merge)
 // the formatter's part of a call's kernel arguments (on the calling context's bound state)
 int fq_bam_device_prepare(fq_bam *b, FqBamArgs *a) {
   std::lock_guard<std::mutex> lk(b->dev_mu);
@@ -233,21 +291,339 @@ static int format_last(fq_bam_t *b, fq_ctx_t *c) {
   fq_host_records(A.s.n_surv, [&](int idx) { fq_bam_fill_thread(A, idx); });
   return FQ_OK;
 }
+// ---- sorted writer: taking runs --------------------------------------------------------------------------------------------------
+// `len` bytes of whole records as one run; ents: the entries that came with them from the device (then the records are in key order), or nullptr
+// take: the vector that holds data, which the run keeps instead of copying it (or nullptr)
+static int sort_add_run(fq_bam_t *b, const uint8_t *data, uint64_t len, const FqBamSortEnt *ents, uint64_t n_ents, std::vector<uint8_t> *take = nullptr) {
+  SortWriter &S = *b->sort;
+  SortRun run;
+  run.n_bytes = len;
+  if (ents) {
+    for (uint64_t i = 0; i < n_ents; ++i) if (ents[i].len) run.ent.push_back(ents[i]);      // (a single-end call keeps the pair layout: its second records are empty)
+    run.device_sorted = true;
+    uint64_t sum = 0;
+    for (const FqBamSortEnt &e : run.ent) sum += e.len;
+    if (sum != len) { b->err = "sorted BAM: a device-sorted run's entries do not add up to its bytes"; return FQ_EINVAL; }
+  }
+  else {
+    for (uint64_t p = 0; p < len;) {      // the host loop over the body launch_bam_key runs
+      if (len - p < 4) { b->err = "sorted BAM: a run does not end with a whole record"; return FQ_EINVAL; }
+      const uint64_t rl = (uint64_t)fq_sort_ld32(data + p) + 4;
+      if (rl < 36 || rl > len - p) { b->err = "sorted BAM: a run does not hold whole records"; return FQ_EINVAL; }
+      run.ent.push_back(fq_bam_sort_entry(data + p, (uint32_t)rl, S.n_ref, S.pos_bits));
+      p += rl;
+    }
+  }
+  if (S.records + run.ent.size() > 0xffffffffull) { b->err = "sorted BAM: more than 2^32 - 1 records (the merge's ordinals are 32 bits wide)"; return FQ_ELIMIT; }
+  if (len && S.mem_used + len > S.mem_limit) {      // raw into a file of its own, read back with pread at close
+    char suffix[32];
+    snprintf(suffix, sizeof suffix, ".tmp.%04d", S.n_tmp++);
+    run.path = S.path + suffix;
+    run.fd = ::open(run.path.c_str(), O_CREAT | O_TRUNC | O_RDWR, 0644);
+    bool ok = run.fd >= 0;
+    for (uint64_t p = 0; ok && p < len;) { const ssize_t w = ::write(run.fd, data + p, (size_t)std::min<uint64_t>(len - p, (uint64_t)1 << 30)); if (w <= 0) ok = false; else p += (uint64_t)w; }
+    if (!ok) { if (run.fd >= 0) ::close(run.fd); ::unlink(run.path.c_str()); b->err = "sorted BAM: cannot write " + run.path; return FQ_EIO; }
+    ::close(run.fd); run.fd = -1;      // (opened again for the close: a long job makes more runs than a process may hold files open)
+    ++S.st.spilled_runs;
+  } else if (len) { if (take) run.bytes = std::move(*take); else run.bytes.assign(data, data + len); S.mem_used += len; }
+  S.records += run.ent.size();
+  ++S.st.runs; S.st.device_sorted_runs += run.device_sorted ? 1 : 0; S.st.records = (int64_t)S.records;
+  S.runs.push_back(std::move(run));
+  return FQ_OK;
+}
+extern "C" int fq_bam_sort_stats(const fq_bam_t *b, fq_bam_sort_stats_t *out) {
+  if (!b || !out || !b->sort) return FQ_EINVAL;
+  *out = b->sort->st;
+  return FQ_OK;
+}
+static_assert(sizeof(fq_bam_sort_ent_t) == sizeof(FqBamSortEnt), "the public entry is fq_sort.h's");
+extern "C" int64_t fq_bam_sort_run_entries(const fq_bam_t *b, int64_t run, fq_bam_sort_ent_t *out, int64_t cap) {
+  if (!b || !b->sort || cap < 0 || (cap > 0 && !out)) return FQ_EINVAL;
+  const int64_t n_runs = (int64_t)b->sort->runs.size();
+  if (run < 0) run += n_runs;
+  if (run < 0 || run >= n_runs) return FQ_EINVAL;
+  const std::vector<FqBamSortEnt> &e = b->sort->runs[(size_t)run].ent;
+  if (!e.empty() && cap > 0) memcpy(out, e.data(), (size_t)std::min<int64_t>(cap, (int64_t)e.size()) * sizeof(FqBamSortEnt));
+  return (int64_t)e.size();
+}
+extern "C" int fq_bam_sort_stats_at_close(fq_bam_t *b, fq_bam_sort_stats_t *out) {
+  if (!b || !b->sort) return FQ_EINVAL;
+  b->sort->at_close = out;
+  return FQ_OK;
+}
+
+// ---- the device's part of the sort and of the close: one bound state, its buffers kept for as long as the scope lives ------------------------------
+namespace {
+struct DevScope {
+  fqdev::State *s = nullptr;
+  std::vector<void *> d, h;
+  explicit DevScope(int device) : s(fqdev::state_create(device)) {}
+  bool bind() { return s && !fqdev::bind(s); }
+  template <class T> T *dm(size_t n) { void *p = fqdev::dmalloc(n * sizeof(T)); if (p) d.push_back(p); return (T *)p; }
+  template <class T> T *hm(size_t n) { void *p = fqdev::hmalloc(n * sizeof(T)); if (p) h.push_back(p); return (T *)p; }
+  void release(void *p) { auto it = std::find(d.begin(), d.end(), p); if (it != d.end()) { fqdev::dfree(p); d.erase(it); } }
+  ~DevScope() { if (s) { (void)fqdev::bind(s); (void)fqdev::sync(); } for (void *p : d) fqdev::dfree(p); for (void *p : h) fqdev::hfree(p); fqdev::state_destroy(s); }
+};
+// perm[i] = the place in keys of the i-th key in stable ascending order (on the bound state; its buffers are freed again)
+int sort_keys_bound(DevScope &D, const uint64_t *keys, uint32_t n, int key_bits, uint32_t *perm, double *kernel_ms) {
+  if (kernel_ms) *kernel_ms = 0;
+  if (!n) return FQ_OK;
+  const size_t nh = (size_t)FQ_SORT_DIGITS * fq_sort_tiles(n);
+  uint64_t *k_in = D.dm<uint64_t>(n), *k_out = D.dm<uint64_t>(n), *k_tmp = D.dm<uint64_t>(n), *hoff = D.dm<uint64_t>(nh + 2);
+  uint32_t *p_out = D.dm<uint32_t>(n), *p_tmp = D.dm<uint32_t>(n), *hist = D.dm<uint32_t>(nh + 1);
+  int rc = FQ_OK;
+  if (!k_in || !k_out || !k_tmp || !hoff || !p_out || !p_tmp || !hist) rc = FQ_ENOMEM;
+  else {
+    const FqSortScratch sc{k_tmp, p_tmp, hist, hoff};
+    if (fqdev::h2d(k_in, keys, (size_t)n * 8) || fqdev::launch_sort_pairs(k_in, n, key_bits, k_out, p_out, sc) || fqdev::d2h(perm, p_out, (size_t)n * 4) || fqdev::sync()) rc = FQ_ENODEV;
+    double ms[FQ_KX_COUNT] = {0}; uint64_t ln[FQ_KX_COUNT] = {0};
+    fqdev::time_collect(ms, ln, FQ_KX_COUNT);
+    if (kernel_ms) *kernel_ms = ms[FQ_KX_SORT];
+  }
+  for (void *p : {(void *)k_in, (void *)k_out, (void *)k_tmp, (void *)hoff, (void *)p_out, (void *)p_tmp, (void *)hist}) D.release(p);
+  return rc;
+}
+// reg2bin of the SAM specification (5.3): the bin of the zero-based half-open interval [beg, end)
+int reg2bin(int64_t beg, int64_t end) {
+  --end;
+  if (beg >> 14 == end >> 14) return (int)(((1 << 15) - 1) / 7 + (beg >> 14));
+  if (beg >> 17 == end >> 17) return (int)(((1 << 12) - 1) / 7 + (beg >> 17));
+  if (beg >> 20 == end >> 20) return (int)(((1 << 9) - 1) / 7 + (beg >> 20));
+  if (beg >> 23 == end >> 23) return (int)(((1 << 6) - 1) / 7 + (beg >> 23));
+  if (beg >> 26 == end >> 26) return (int)(((1 << 3) - 1) / 7 + (beg >> 26));
+  return 0;
+}
+void put32(std::vector<uint8_t> &v, uint32_t x) { for (int k = 0; k < 4; ++k) v.push_back((uint8_t)(x >> (8 * k))); }
+void put64(std::vector<uint8_t> &v, uint64_t x) { for (int k = 0; k < 8; ++k) v.push_back((uint8_t)(x >> (8 * k))); }
+}  // namespace
+
+extern "C" int fq_sort_keys_device(int device, const uint64_t *keys, int64_t n, int key_bits, uint32_t *perm, double *kernel_ms) {
+  if (n < 0 || n > 0xffffffffll || key_bits < 1 || key_bits > 64 || (n > 0 && (!keys || !perm))) return FQ_EINVAL;
+  DevScope D(device);
+  if (!D.bind()) return FQ_ENODEV;
+  return sort_keys_bound(D, keys, (uint32_t)n, key_bits, perm, kernel_ms);
+}
+
+// ---- sorted writer: the close ------------------------------------------------------------------------------------------------------
+// The total order is the device's sort again: the runs' keys behind each other in run order, sorted stably with the global ordinal as payload, so that
+// ties fall in input order across runs (no heap merge on the host).  The header's members have gone through the host BGZF layer; the merged record stream
+// is assembled in slices of whole members by several threads (each a contiguous range of output bytes), compressed by the compressor the unsorted writer
+// uses -- the device's members, or zlib under FASTQUICK_BAM_HOST_DEFLATE -- on ONE device state that lives for the whole close, and written in order.
+// The index's virtual offsets come from the BSIZE fields of the members that came back.
+static int sort_close(fq_bam_t *b) {
+  SortWriter &S = *b->sort;
+  const double t_begin = now_sec();
+  const uint64_t N = S.records;
+  DevScope D(b->ix->device);
+  if (!D.bind()) { b->err = std::string("sorted BAM: ") + fqdev::last_error(); return FQ_ENODEV; }
+  for (SortRun &R : S.runs)
+    if (!R.path.empty() && (R.fd = ::open(R.path.c_str(), O_RDONLY)) < 0) { b->err = "sorted BAM: cannot open " + R.path + " again"; return FQ_EIO; }
+  // 1. the order
+  std::vector<uint64_t> run_base(S.runs.size() + 1, 0);
+  std::vector<uint32_t> perm((size_t)N);
+  {
+    std::vector<uint64_t> keys((size_t)N);
+    uint64_t g = 0;
+    for (size_t r = 0; r < S.runs.size(); ++r) {
+      SortRun &R = S.runs[r];
+      run_base[r] = g;
+      R.off.resize(R.ent.size() + 1);
+      uint64_t o = 0;
+      for (size_t j = 0; j < R.ent.size(); ++j) { keys[g++] = R.ent[j].key; R.off[j] = o; o += R.ent[j].len; }
+      R.off[R.ent.size()] = o;
+      if (o != R.n_bytes) { b->err = "sorted BAM: a run's entries do not add up to its bytes"; return FQ_EINVAL; }
+    }
+    run_base[S.runs.size()] = g;
+    double ms = 0;
+    const int rc = sort_keys_bound(D, keys.data(), (uint32_t)N, S.key_bits, perm.data(), &ms);
+    if (rc) { b->err = std::string("sorted BAM: the key sort failed: ") + fqdev::last_error(); return rc; }
+    S.st.sort_kernel_ms += ms;
+  }
+  const double t_sorted = now_sec();
+  // 2. where every record of the output comes from and goes to
+  std::vector<FqBamSortEnt> se((size_t)N);
+  std::vector<uint32_t> src_run((size_t)N);
+  std::vector<uint64_t> src_off((size_t)N), ooff((size_t)N + 1);
+  std::vector<uint8_t> unmapped((size_t)N, 0);
+  {
+    uint64_t o = 0;
+    for (uint64_t i = 0; i < N; ++i) {
+      const uint64_t g = perm[i];
+      const size_t r = (size_t)(std::upper_bound(run_base.begin(), run_base.end() - 1, g) - run_base.begin()) - 1;
+      const SortRun &R = S.runs[r];
+      se[i] = R.ent[g - run_base[r]]; src_run[i] = (uint32_t)r; src_off[i] = R.off[g - run_base[r]];
+      ooff[i] = o; o += se[i].len;
+    }
+    ooff[N] = o;
+  }
+  std::vector<uint32_t>().swap(perm);
+  const uint64_t total = ooff[N];
+  // 3. the record stream, slice by slice
+  b->z.flush_all();
+  if (!b->z.ok) return FQ_EIO;
+  uint64_t fpos = (uint64_t)ftello(b->z.fp);
+  const uint64_t n_mem = (total + FQD_BLOCK - 1) / FQD_BLOCK;
+  std::vector<uint64_t> member_off((size_t)n_mem + 1);
+  const uint32_t SLB = 256;                                   // members per slice
+  const size_t SL = (size_t)SLB * FQD_BLOCK;
+  const bool on_device = !b->host_deflate;
+  uint8_t *p_in = D.hm<uint8_t>(SL + 64), *p_out = D.hm<uint8_t>((size_t)SLB * FQD_SLOT);
+  uint8_t *d_in = nullptr, *d_stage = nullptr, *d_out = nullptr; uint32_t *d_bs = nullptr; uint64_t *d_off = nullptr;
+  if (!p_in || !p_out) { b->err = "sorted BAM: out of pinned host memory"; return FQ_ENOMEM; }
+  if (on_device && total) {
+    d_in = D.dm<uint8_t>(SL + 64); d_stage = D.dm<uint8_t>((size_t)SLB * FQD_SLOT); d_out = D.dm<uint8_t>((size_t)SLB * FQD_SLOT);
+    d_bs = D.dm<uint32_t>(SLB + 1); d_off = D.dm<uint64_t>(SLB + 2);
+    if (!d_in || !d_stage || !d_out || !d_bs || !d_off) { b->err = "sorted BAM: out of device memory"; return FQ_ENOMEM; }
+    if (!fqdev::crc_const()) { b->err = std::string("BGZF on the device: ") + fqdev::last_error(); return FQ_ENODEV; }
+  }
+  double t_assemble = 0, t_compress = 0;
+  std::atomic<bool> read_bad{false};
+  auto read_src = [&](uint64_t i, uint64_t at, uint64_t n, uint8_t *dst) {      // n bytes of output record i from byte `at` of it
+    const SortRun &R = S.runs[src_run[i]];
+    if (R.fd < 0) { memcpy(dst, R.bytes.data() + src_off[i] + at, (size_t)n); return; }
+    for (uint64_t got = 0; got < n;) { const ssize_t k = ::pread(R.fd, dst + got, (size_t)(n - got), (off_t)(src_off[i] + at + got)); if (k <= 0) { read_bad = true; return; } got += (uint64_t)k; }
+  };
+  auto assemble = [&](uint64_t lo, uint64_t hi, uint64_t s0) {                   // output bytes [lo, hi) into p_in - s0
+    uint64_t i = (uint64_t)(std::upper_bound(ooff.begin(), ooff.end(), lo) - ooff.begin()) - 1;
+    for (uint64_t pos = lo; pos < hi; ++i) {
+      const uint64_t at = pos - ooff[i], n = std::min(ooff[i + 1], hi) - pos;
+      read_src(i, at, n, p_in + (pos - s0));
+      if (at == 0) {                                                            // whoever copies a record's first byte notes its flag 4 for the index
+        uint8_t f[2];
+        if (n >= 20) memcpy(f, p_in + (pos - s0) + 18, 2); else read_src(i, 18, 2, f);
+        unmapped[i] = (f[0] & 4) ? 1 : 0;
+      }
+      pos += n;
+    }
+  };
+  for (uint64_t s0 = 0, m0 = 0; s0 < total; s0 += SL, m0 += SLB) {
+    const uint64_t n = std::min<uint64_t>(SL, total - s0);
+    const uint32_t nb = (uint32_t)((n + FQD_BLOCK - 1) / FQD_BLOCK);
+    const double ta = now_sec();
+    {
+      const uint64_t T = std::min<uint64_t>(Bgzf::kThreads, (n + 65535) / 65536), per = (n + T - 1) / T;
+      std::vector<std::thread> th;
+      for (uint64_t t = 1; t < T; ++t) { const uint64_t lo = s0 + t * per, hi = std::min(s0 + n, lo + per); if (lo < hi) th.emplace_back(assemble, lo, hi, s0); }
+      assemble(s0, std::min(s0 + n, s0 + per), s0);
+      for (auto &x : th) x.join();
+    }
+    if (read_bad) { b->err = "sorted BAM: reading a spilled run back failed"; return FQ_EIO; }
+    const double tc = now_sec();
+    t_assemble += tc - ta;
+    uint64_t zn = 0;
+    if (on_device) {
+      FqDeflateArgs a{d_in, n, d_stage, d_bs, fqdev::crc_const(), nb};
+      FqDeflatePackArgs pk{d_stage, d_bs, d_off, d_out, nb};
+      if (fqdev::h2d(d_in, p_in, (size_t)n) || fqdev::launch_deflate(a) || fqdev::launch_scan(d_bs, d_off, nb) || fqdev::launch_deflate_pack(pk) || fqdev::d2h(&zn, d_off + nb, 8) || fqdev::sync() ||
+          zn > (uint64_t)SLB * FQD_SLOT || fqdev::d2h(p_out, d_out, (size_t)zn) || fqdev::sync()) { b->err = std::string("sorted BAM: BGZF on the device: ") + fqdev::last_error(); return FQ_ENODEV; }
+    } else {
+      std::vector<Bgzf::Out> outs(nb);
+      std::vector<char> good(nb, 0);
+      auto work = [&](uint32_t lo, uint32_t hi) { for (uint32_t k = lo; k < hi; ++k) good[k] = Bgzf::compress_block(p_in + (size_t)k * FQD_BLOCK, (size_t)std::min<uint64_t>(FQD_BLOCK, n - (uint64_t)k * FQD_BLOCK), outs[k]); };
+      const uint32_t T = std::min<uint32_t>(Bgzf::kThreads, nb), per = (nb + T - 1) / T;
+      std::vector<std::thread> th;
+      for (uint32_t t = 0; t < T; ++t) { const uint32_t lo = t * per, hi = std::min(nb, lo + per); if (lo < hi) th.emplace_back(work, lo, hi); }
+      for (auto &x : th) x.join();
+      for (uint32_t k = 0; k < nb; ++k) { if (!good[k]) { b->err = "sorted BAM: zlib failed"; return FQ_EIO; } memcpy(p_out + zn, outs[k].d, outs[k].n); zn += outs[k].n; }
+    }
+    uint64_t p = 0;
+    for (uint32_t k = 0; k < nb; ++k) {                        // the members' sizes as the file holds them: BSIZE
+      if (p + 18 > zn) { b->err = "sorted BAM: the compressor returned fewer members than blocks"; return FQ_EIO; }
+      member_off[(size_t)(m0 + k)] = fpos + p;
+      p += (uint64_t)fq_sort_ld16(p_out + p + 16) + 1;
+    }
+    if (p != zn) { b->err = "sorted BAM: the members' sizes do not add up"; return FQ_EIO; }
+    b->z.write_members(p_out, (size_t)zn);
+    if (!b->z.ok) return FQ_EIO;
+    fpos += zn;
+    t_compress += now_sec() - tc;
+  }
+  member_off[(size_t)n_mem] = fpos;
+  const uint64_t eof_voff = fpos << 16;
+  b->z.close();                                                // (nothing buffered: the end-of-file block)
+  if (!b->z.ok) return FQ_EIO;
+  const double t_written = now_sec();
+  // 4. the index (SAM specification 5.2)
+  auto voff = [&](uint64_t i) { return i >= N ? eof_voff : member_off[(size_t)(ooff[i] / FQD_BLOCK)] << 16 | ooff[i] % FQD_BLOCK; };
+  std::vector<uint8_t> bai;
+  bai.insert(bai.end(), {'B', 'A', 'I', 1});
+  put32(bai, (uint32_t)S.n_ref);
+  uint64_t i = 0, n_no_coor = 0;
+  const uint64_t pos_mask = ((uint64_t)1 << S.pos_bits) - 1;
+  for (int ref = 0; ref < S.n_ref; ++ref) {
+    std::map<uint32_t, std::vector<std::pair<uint64_t, uint64_t>>> bins;
+    std::vector<uint64_t> lin;
+    uint64_t off_beg = 0, off_end = 0, n_map = 0, n_unmap = 0;
+    uint32_t last_bin = 0xffffffffu;
+    bool any = false;
+    for (; i < N && (int64_t)(se[i].key >> (S.pos_bits + 1)) == ref; ++i) {
+      const int64_t beg = std::max<int64_t>((int64_t)(se[i].key >> 1 & pos_mask) - 1, 0), end = std::max<int64_t>(se[i].end, beg + 1);
+      const uint64_t v0 = voff(i), v1 = voff(i + 1);
+      const uint32_t bin = (uint32_t)reg2bin(beg, end);
+      if (bin == last_bin) bins[bin].back().second = v1;        // consecutive records of one bin share a chunk
+      else bins[bin].emplace_back(v0, v1);
+      last_bin = bin;
+      const size_t w1 = (size_t)((end - 1) >> 14);
+      if (lin.size() <= w1) lin.resize(w1 + 1, 0);
+      for (size_t w = (size_t)(beg >> 14); w <= w1; ++w) if (!lin[w]) lin[w] = v0;      // (offsets ascend: the first record seen is the smallest)
+      if (!any) { off_beg = v0; any = true; }
+      off_end = v1;
+      if (unmapped[i]) ++n_unmap; else ++n_map;
+    }
+    for (size_t w = lin.size(); w-- > 1;) if (!lin[w - 1]) lin[w - 1] = lin[w];           // a window no record overlaps: the next later window's value
+    put32(bai, (uint32_t)(bins.size() + (any ? 1 : 0)));
+    for (const auto &kv : bins) {
+      put32(bai, kv.first); put32(bai, (uint32_t)kv.second.size());
+      for (const auto &c : kv.second) { put64(bai, c.first); put64(bai, c.second); }
+    }
+    if (any) { put32(bai, 37450); put32(bai, 2); put64(bai, off_beg); put64(bai, off_end); put64(bai, n_map); put64(bai, n_unmap); }
+    put32(bai, (uint32_t)lin.size());
+    for (uint64_t v : lin) put64(bai, v);
+  }
+  n_no_coor = N - i;
+  put64(bai, n_no_coor);
+  {
+    const std::string path = S.path + ".bai";
+    FILE *f = fopen(path.c_str(), "wb");
+    const bool ok = f && fwrite(bai.data(), 1, bai.size(), f) == bai.size();
+    if (f && fclose(f)) { b->err = "sorted BAM: cannot write " + path; return FQ_EIO; }
+    if (!ok) { b->err = "sorted BAM: cannot write " + path; return FQ_EIO; }
+  }
+  const double t_end = now_sec();
+  S.st.close_sec = t_end - t_begin; S.st.close_sort_sec = t_sorted - t_begin; S.st.close_assemble_sec = t_assemble; S.st.close_compress_sec = t_compress;
+  S.st.close_index_sec = t_end - t_written;
+  if (S.at_close) *S.at_close = S.st;
+  return FQ_OK;
+}
+
 extern "C" int fq_bam_add_last(fq_bam_t *b, fq_ctx_t *c) {
   if (!b || !c || !b->z.fp) return FQ_EINVAL;
   if (const FqBamCallOut *D = fq_ctx_bam_out(c)) {        // the records were formatted by the call's kernels (fq_ctx_attach_bam): they only leave the device here
     if (D->owner != b || !D->ready) { b->err = "fq_bam_add_last: the context's last call formatted its records for another writer, or failed"; return FQ_EINVAL; }
     if (fq_ctx_emit_wait(c)) { b->err = "fq_bam_add_last: waiting for the call's kernels failed"; return FQ_ENODEV; }      // (z_bytes comes back with them)
+    if (b->sort) {          // a run of the sorted writer: the call sorted its records (emit_fill); they arrive in key order with their entries
+      if (!D->sorted && D->bytes) { b->err = "fq_bam_add_last: the call left no sorted run"; return FQ_EINVAL; }
+      const fq_sink_fn append = [](void *user, const void *d, int64_t l) -> int { auto *v = (std::vector<uint8_t> *)user; v->insert(v->end(), (const uint8_t *)d, (const uint8_t *)d + l); return 0; };
+      std::vector<uint8_t> ent, rec;      // (rec becomes the run's bytes: fetched once, not copied again)
+      if (D->bytes) {
+        rec.reserve((size_t)D->bytes); ent.reserve((size_t)D->n_rec * sizeof(FqBamSortEnt));
+        if (fq_ctx_bam_stream(c, append, &rec, FQ_BAM_STREAM_SORTED) < 0 || fq_ctx_bam_stream(c, append, &ent, FQ_BAM_STREAM_ENTRIES) < 0) { b->err = "fq_bam_add_last: fetching the sorted run from the device failed"; return FQ_ENODEV; }
+      }
+      b->sort->st.sort_kernel_ms += D->sort_ms; b->sort->st.gather_kernel_ms += D->gather_ms;
+      static const FqBamSortEnt none{};      // (an empty call: a device-sorted run without records)
+      return sort_add_run(b, rec.data(), rec.size(), ent.empty() ? &none : (const FqBamSortEnt *)ent.data(), ent.size() / sizeof(FqBamSortEnt), &rec);
+    }
     int64_t n;
     if (D->z_bytes) {       // finished BGZF members (fq_deflate.h): appended behind whatever the host's layer still holds
       b->z.flush_all();
-      n = fq_ctx_bam_stream(c, [](void *user, const void *data, int64_t len) -> int { ((fq_bam *)user)->z.write_members(data, (size_t)len); return ((fq_bam *)user)->z.ok ? 0 : 1; }, b, 1);
+      n = fq_ctx_bam_stream(c, [](void *user, const void *data, int64_t len) -> int { ((fq_bam *)user)->z.write_members(data, (size_t)len); return ((fq_bam *)user)->z.ok ? 0 : 1; }, b, FQ_BAM_STREAM_MEMBERS);
     } else n = fq_ctx_bam_stream(c, [](void *user, const void *data, int64_t len) -> int { ((fq_bam *)user)->z.write(data, (size_t)len); return ((fq_bam *)user)->z.ok ? 0 : 1; }, b, 0);
     if (n < 0) { b->err = "fq_bam_add_last: fetching the records from the device failed"; return (int)n; }
     return b->z.ok ? FQ_OK : FQ_EIO;
   }
   const int rc = format_last(b, c);
   if (rc) return rc;
+  if (b->sort) return sort_add_run(b, b->last.data(), b->last.size(), nullptr, 0);
   if (!b->last.empty()) b->z.write(b->last.data(), b->last.size());
   return b->z.ok ? FQ_OK : FQ_EIO;
 }
@@ -271,6 +647,7 @@ extern "C" int fq_bam_format_last(fq_bam_t *b, fq_ctx_t *c, const void **data, i
 }
 extern "C" int fq_bam_write_records(fq_bam_t *b, const void *data, int64_t len) {
   if (!b || !b->z.fp || len < 0 || (len > 0 && !data)) return FQ_EINVAL;
+  if (b->sort) return sort_add_run(b, (const uint8_t *)data, (uint64_t)len, nullptr, 0);
   if (len) b->z.write(data, (size_t)len);
   return b->z.ok ? FQ_OK : FQ_EIO;
 }
@@ -308,6 +685,13 @@ extern "C" int fq_bgzf_deflate_device(int device, const uint8_t *in, int64_t n, 
 
 extern "C" int fq_bam_close(fq_bam_t *b) {
   if (!b) return FQ_EINVAL;
+  if (b->sort) {
+    const int rc = sort_close(b);
+    if (rc) fprintf(stderr, "fq_bam_close: %s\n", b->err.c_str());
+    if (b->z.fp) { fclose(b->z.fp); b->z.fp = nullptr; }      // (after a failed close; the runs' files go with the writer)
+    delete b;
+    return rc;
+  }
   b->z.close();
   const bool ok = b->z.ok;
   delete b;

@@ -95,6 +95,9 @@ struct Args {
   std::string devices;   // --devices: several devices, the lines of --fq_list dealt over them
   int pack_threads = std::min(32, std::max(1, fq_host_cpus()));     // host threads of the FASTQ readers (half per file) and of the packer, from the CPUs the process may use; --t sets it
   bool clean_names = false;
+  bool sorted_bam = false;       // --sorted_bam: <out_prefix>.sorted.bam in coordinate order and its .bai instead of <out_prefix>.bam (fq_bam_create_sorted: what the pipeline's samtools sort / index steps made of O.bam)
+  long long sort_mem = 4ll << 30; // --sort_mem: bytes of records the sorted writer keeps in host memory before its runs go to files
+  std::string bam_file() const { return out_prefix + (sorted_bam ? ".sorted.bam" : ".bam"); }
   bool host_consumers = false;   // --host_consumers: SAM text and StatCollector's sums on the host's threads from the result arrays (round 5's way; the default runs them in kernels, fq_emit.h)
   bool host_reader = false;   // --host_reader: the FASTQ front end on the host's threads also for BGZF files (the default inflates and tokenises them on the device)
   bool strict = false;   // --strict_reference: stop where the output could differ from the reference's bytes (today: QUAL of reads of unequal lengths)
@@ -105,7 +108,7 @@ struct Args {
 };
 
 int usage() {
-  fprintf(stderr, "Usage: FASTQuick_amd align --index_prefix P --fastq_1 R1.fq[.gz] [--fastq_2 R2.fq[.gz]] | --fq_list LIST  --out_prefix O [--sam_out] [--RG STR] [--cal_dup]\n"
+  fprintf(stderr, "Usage: FASTQuick_amd align --index_prefix P --fastq_1 R1.fq[.gz] [--fastq_2 R2.fq[.gz]] | --fq_list LIST  --out_prefix O [--sam_out | --sorted_bam [--sort_mem BYTES]] [--RG STR] [--cal_dup]\n"
                   "                       [--q INT] [--n FLOAT|INT] [--kmer_thresh INT] [--o INT] [--e INT] [--i INT] [--d INT] [--l INT] [--k INT]\n"
                   "                       [--m INT] [--R INT] [--N] [--L] [--I] [--max_isize INT] [--max_occ INT] [--is_sw] [--n_multi INT] [--N_multi INT]\n"
                   "                       [--ap_prior FLOAT] [--force_isize] [--frac_samp FLOAT] [--t INT] [--chunk_pairs INT] [--batch_pairs INT] [--device INT | --devices LIST] [--read_len INT] [--clean_names] [--strict_reference] [--host_reader] [--host_consumers]\n"
@@ -231,7 +234,7 @@ struct Sink {
 };
 Sink direct_sink(const Args &A) {   // (.bam: set once the writer is there)
   Sink s;
-  s.sam_fp = A.sam_out ? stdout : nullptr; s.what = A.sam_out ? "the SAM text" : A.out_prefix + ".bam";
+  s.sam_fp = A.sam_out ? stdout : nullptr; s.what = A.sam_out ? "the SAM text" : A.bam_file();
   return s;
 }
 // The records of the context's last call, to the sink: SAM text formatted on the device or by the host, or BAM records.
@@ -316,10 +319,18 @@ void append_file(const std::string &path, FILE *to, fq_bam_t *bam) {   // a part
   FILE *f = fopen(path.c_str(), "rb");
   if (!f) die("cannot reopen " + path);
   std::vector<char> buf((size_t)8 << 20);
-  size_t n;
-  while ((n = fread(buf.data(), 1, buf.size(), f)) > 0) {
-    if (to ? fwrite(buf.data(), 1, n, to) != n : fq_bam_write_records(bam, buf.data(), (int64_t)n) != 0) die("appending " + path + " to the output failed");
+  size_t n, held = 0;      // (BAM records go on whole: a sorted writer takes every piece as a run of records; what a read cut off waits for the next)
+  while ((n = fread(buf.data() + held, 1, buf.size() - held, f)) > 0) {
+    n += held; held = 0;
+    if (to) { if (fwrite(buf.data(), 1, n, to) != n) die("appending " + path + " to the output failed"); continue; }
+    size_t whole = 0;
+    for (uint32_t bs; whole + 4 <= n && (memcpy(&bs, buf.data() + whole, 4), whole + 4 + (size_t)bs <= n);) whole += 4 + (size_t)bs;
+    if (whole && fq_bam_write_records(bam, buf.data(), (int64_t)whole) != 0) die("appending " + path + " to the output failed");
+    held = n - whole;
+    if (held == buf.size()) die("appending " + path + " to the output failed: a record larger than the buffer");
+    memmove(buf.data(), buf.data() + whole, held);
   }
+  if (held) die("appending " + path + " to the output failed: the file ends inside a record");
   fclose(f);
   remove(path.c_str());
 }
@@ -793,6 +804,24 @@ bool pick_devices(Run &R) {
   R.wk = std::vector<Worker>(R.devices.size());
   return shard_one_pair;
 }
+// The writer of the run's BAM file: <out_prefix>.bam in input order, or with --sorted_bam <out_prefix>.sorted.bam in coordinate order with its index.
+int create_bam_file(const Args &A, const char *path, const fq_index_t *ix, const std::string &fai, const fq_qc_opts_t *qo, fq_bam_t **out) {
+  if (A.sorted_bam) return fq_bam_create_sorted(ix, fai.c_str(), path, A.rg.c_str(), qo, A.sort_mem, out);
+  return fq_bam_create(ix, fai.c_str(), path, A.rg.c_str(), qo, out);
+}
+// ... and its close; a sorted writer says what it held and where the close's time went
+bool close_bam_file(const Args &A, fq_bam_t *bam) {
+  fq_bam_sort_stats_t st{};
+  if (A.sorted_bam) fq_bam_sort_stats_at_close(bam, &st);
+  if (fq_bam_close(bam)) return false;
+  if (A.sorted_bam) {
+    fprintf(stderr, "NOTICE - sorted BAM: %lld records in %lld runs (%lld sorted on the device inside their calls, %lld spilled to files); keys of %d bits\n", (long long)st.records, (long long)st.runs,
+            (long long)st.device_sorted_runs, (long long)st.spilled_runs, st.key_bits);
+    fprintf(stderr, "NOTICE - sorted BAM: entries and sort kernels %.3f ms (the calls' runs and the close's key sort) ; gather kernels %.3f ms (the calls' runs) ; close %.3f s (key sort %.3f ; assembly %.3f ; compression and writing %.3f ; index %.3f)\n", st.sort_kernel_ms,
+            st.gather_kernel_ms, st.close_sec, st.close_sort_sec, st.close_assemble_sec, st.close_compress_sec, st.close_index_sec);
+  }
+  return true;
+}
 // Worker w: the index onto its device, its QC consumer (files under qc_prefix) and its BAM writer (bam_path null: a formatter without a file).
 void open_worker(Run &R, size_t w, const std::string &qc_prefix, const char *bam_path) {
   const Args &A = R.A;
@@ -809,8 +838,8 @@ void open_worker(Run &R, size_t w, const std::string &qc_prefix, const char *bam
     mark("QC consumer set up");
   }
   if (!A.sam_out) {
-    rc = fq_bam_create(K.ix, R.fai.c_str(), bam_path, A.rg.c_str(), &R.qo, &K.bam);
-    if (rc) die("cannot open " + A.out_prefix + ".bam / " + R.fai + " (" + std::to_string(rc) + ")");
+    rc = bam_path ? create_bam_file(A, bam_path, K.ix, R.fai, &R.qo, &K.bam) : fq_bam_create(K.ix, R.fai.c_str(), nullptr, A.rg.c_str(), &R.qo, &K.bam);
+    if (rc) die("cannot open " + std::string(bam_path ? bam_path : "a BAM formatter") + " / " + R.fai + " (" + std::to_string(rc) + ")");
     mark("BAM writer set up");
   }
 }
@@ -822,13 +851,13 @@ Merged open_merged(Run &R) {
   Merged M;
   M.out = direct_sink(A);
   if (A.sam_out) write_sam_header(R.wk[0].ix);
-  else if (fq_bam_create(R.wk[0].ix, R.fai.c_str(), (A.out_prefix + ".bam").c_str(), A.rg.c_str(), &R.qo, &M.out.bam)) die("cannot open " + A.out_prefix + ".bam / " + R.fai);
+  else if (create_bam_file(A, A.bam_file().c_str(), R.wk[0].ix, R.fai, &R.qo, &M.out.bam)) die("cannot open " + A.bam_file() + " / " + R.fai);
   if (R.have_qc && fq_qc_create(R.wk[0].ix, R.pre.c_str(), A.out_prefix.c_str(), &R.qo, &M.qc)) die("cannot set up the QC consumer");
   return M;
 }
 void close_merged(Run &R, Merged &M) {   // ... and the workers' objects go
   M.out.flush();
-  if (M.out.bam && fq_bam_close(M.out.bam)) die("closing " + R.A.out_prefix + ".bam failed");
+  if (M.out.bam && !close_bam_file(R.A, M.out.bam)) die("closing " + R.A.bam_file() + " failed");
   if (M.qc) {
     if (fq_qc_write(M.qc)) die("writing the QC files failed");
     fq_qc_destroy(M.qc);
@@ -852,7 +881,7 @@ Args worker_args(const Run &R) {   // the host's CPUs are shared by the workers
 void run_one_device(Run &R) {
   const Args &A = R.A;
   Worker &K = R.wk[0];
-  const std::string bam_path = A.out_prefix + ".bam";
+  const std::string bam_path = A.bam_file();
   std::thread opener([&] { open_worker(R, 0, A.out_prefix, A.sam_out ? nullptr : bam_path.c_str()); });
   Sink out = direct_sink(A);
   bool opened = false;
@@ -868,10 +897,10 @@ void run_one_device(Run &R) {
   // (the BAM file's last blocks and its close beside the QC files' writing: a third of a second of a deep run's tail)
   bool bam_bad = false;
   std::thread closer;
-  if (K.bam) closer = std::thread([&] { bam_bad = fq_bam_close(K.bam) != 0; mark("BAM file closed"); });
+  if (K.bam) closer = std::thread([&] { bam_bad = !close_bam_file(A, K.bam); mark("BAM file closed"); });
   const bool qc_bad = K.qc && fq_qc_write(K.qc) != 0;
   if (closer.joinable()) closer.join();
-  if (bam_bad) die("closing " + A.out_prefix + ".bam failed");
+  if (bam_bad) die("closing " + A.bam_file() + " failed");
   if (qc_bad) die("writing the QC files failed");
   mark("QC files written");
   if (K.qc) { fq_qc_t *qc = K.qc; release_later([qc] { fq_qc_destroy(qc); mark("QC consumer released"); }); }      // (beside the contexts' release)
@@ -985,6 +1014,8 @@ int main(int argc, char **argv) {
     else if (f == "--strict_reference") A.strict = true;
     else if (f == "--host_reader") A.host_reader = true;
     else if (f == "--host_consumers") A.host_consumers = true;
+    else if (f == "--sorted_bam") A.sorted_bam = true;
+    else if (f == "--sort_mem") { A.sort_mem = atoll(need("")); if (A.sort_mem < 0) die("--sort_mem must not be negative"); }
     else if (f == "--batch_pairs") A.o.batch_pairs = atoi(need(""));   // READ_BUFFER_SIZE of the run to reproduce (default 262144)
     else if (f == "--device") A.device = atoi(need(""));
     else if (f == "--devices") A.devices = need("");
@@ -1001,6 +1032,7 @@ int main(int argc, char **argv) {
   // whole slot, so with read_len >= 96 -- the reference's own value is 151 -- nothing an earlier read left can reach the 96-base window the
   // read filter looks at, and the re-allocation is invisible; a smaller --read_len would make it visible, and is refused.
   if (A.read_len < 96) die("--read_len must be at least 96 (the reference's is 151): below that its slot re-allocation (src/BwtMapper.cpp:536-546) would show in the read filter, and it is not modelled");
+  if (A.sorted_bam && A.sam_out) die("--sorted_bam writes a BAM file: it cannot be combined with --sam_out (sorting the SAM text is not supported)");
   if (A.out_prefix == "Empty") die("--out_prefix is required");
   if (A.index_prefix == "Empty") die("--index_prefix is required");
   R.inputs = read_inputs(A);

@@ -1633,6 +1633,126 @@ int launch_deflate_pack(const FqDeflatePackArgs &a) {
   FQ_HIP(hipGetLastError());
   return 0;
 }
+// ---- stable LSD radix sort of (key, ordinal) pairs (fq_sort.h) ------------------------------------------------
+// hist[digit][tile]: how many keys of the tile carry the digit in this pass (the counts do not depend on the order the lanes add in)
+__global__ void __launch_bounds__(256) k_sort_hist(const uint64_t *key, uint32_t n, int pass, uint32_t tiles, uint32_t *hist) {
+  __shared__ uint32_t h[FQ_SORT_DIGITS];
+  h[threadIdx.x] = 0;
+  __syncthreads();
+  const uint64_t lo = (uint64_t)blockIdx.x * FQ_SORT_TILE;
+  for (uint32_t r = 0; r < FQ_SORT_TILE / 256; ++r) {
+    const uint64_t i = lo + r * 256u + threadIdx.x;
+    if (i < n) atomicAdd(&h[fq_sort_digit(key[i], pass)], 1u);
+  }
+  __syncthreads();
+  hist[(size_t)threadIdx.x * tiles + blockIdx.x] = h[threadIdx.x];
+}
+// hoff[digit][tile]: where the tile's first key of the digit goes.  A round takes 256 keys in input order: inside a wavefront a lane's rank among the
+// lanes of its digit comes from a ballot match, the wavefronts' counts per digit meet in LDS, then thread d moves digit d's base on and clears its counts.
+__global__ void __launch_bounds__(256) k_sort_scatter(const uint64_t *key_in, const uint32_t *perm_in, uint32_t n, int pass, uint32_t tiles, const uint64_t *hoff,
+                                                      uint64_t *key_out, uint32_t *perm_out) {
+  __shared__ uint64_t base[FQ_SORT_DIGITS];
+  __shared__ uint32_t wcnt[4][FQ_SORT_DIGITS];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
+  base[tid] = hoff[(size_t)tid * tiles + blockIdx.x];
+  wcnt[0][tid] = 0; wcnt[1][tid] = 0; wcnt[2][tid] = 0; wcnt[3][tid] = 0;
+  __syncthreads();
+  const uint64_t lo = (uint64_t)blockIdx.x * FQ_SORT_TILE;
+  for (uint32_t r = 0; r < FQ_SORT_TILE / 256; ++r) {
+    if (lo + r * 256u >= n) break;                   // (the same for every thread of the workgroup)
+    const uint64_t i = lo + r * 256u + tid;
+    const bool valid = i < n;
+    const uint64_t k = valid ? key_in[i] : 0;
+    const uint32_t d = fq_sort_digit(k, pass);
+    unsigned long long same = __ballot(valid);       // the lanes of this wavefront that hold a key with this lane's digit
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+      const unsigned long long bal = __ballot((d >> b) & 1u);
+      same &= ((d >> b) & 1u) ? bal : ~bal;
+    }
+    const uint32_t rank = (uint32_t)__popcll(same & ((1ull << lane) - 1ull)), cnt = (uint32_t)__popcll(same);
+    if (valid && rank == 0) wcnt[wid][d] = cnt;
+    __syncthreads();
+    if (valid) {
+      uint64_t at = base[d] + rank;
+      for (uint32_t w = 0; w < wid; ++w) at += wcnt[w][d];
+      if (at < n) { key_out[at] = k; perm_out[at] = perm_in ? perm_in[i] : (uint32_t)i; }
+    }
+    __syncthreads();
+    base[tid] += (uint64_t)wcnt[0][tid] + wcnt[1][tid] + wcnt[2][tid] + wcnt[3][tid];
+    wcnt[0][tid] = 0; wcnt[1][tid] = 0; wcnt[2][tid] = 0; wcnt[3][tid] = 0;
+    __syncthreads();
+  }
+}
+int launch_sort_pairs(const uint64_t *key_in, uint32_t n, int key_bits, uint64_t *key_out, uint32_t *perm_out, const FqSortScratch &s) {
+  FQ_PRE();
+  if (!n) return 0;
+  const int P = fq_sort_passes(key_bits);
+  const uint32_t tiles = fq_sort_tiles(n);
+  const uint64_t *kin = key_in;
+  const uint32_t *pin = nullptr;
+  for (int p = 0; p < P; ++p) {
+    const bool to_out = ((P - 1 - p) & 1) == 0;      // the last pass lands in key_out / perm_out
+    uint64_t *ko = to_out ? key_out : s.key_tmp;
+    uint32_t *po = to_out ? perm_out : s.perm_tmp;
+    hipEvent_t e0, e1;
+    kernel_events(FQ_KX_SORT, &e0, &e1);
+    hipExtLaunchKernelGGL(k_sort_hist, dim3(tiles), dim3(256), 0, g_stream, e0, e1, 0, kin, n, p, tiles, s.hist);
+    if (const int rc = launch_scan(s.hist, s.hoff, FQ_SORT_DIGITS * tiles)) return rc;
+    kernel_events(FQ_KX_SORT, &e0, &e1);
+    hipExtLaunchKernelGGL(k_sort_scatter, dim3(tiles), dim3(256), 0, g_stream, e0, e1, 0, kin, pin, n, p, tiles, (const uint64_t *)s.hoff, ko, po);
+    kin = ko; pin = po;
+  }
+  FQ_HIP(hipGetLastError());
+  return 0;
+}
+__global__ void __launch_bounds__(256) k_bam_key(FqBamKeyArgs a) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < a.n) fq_bam_key_thread(a, i);
+}
+__global__ void __launch_bounds__(256) k_sort_permute(const FqBamSortEnt *ent, const uint32_t *perm, uint32_t n, FqBamSortEnt *ent_out, uint32_t *len_out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) { const FqBamSortEnt e = ent[perm[i]]; ent_out[i] = e; len_out[i] = e.len; }
+}
+__global__ void __launch_bounds__(256) k_bam_gather(FqBamGatherArgs a, uint64_t n) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  if (t * 16 + 16 <= a.total) fq_bam_gather_piece16(a, t); else fq_bam_gather_piece(a, t);
+}
+__global__ void __launch_bounds__(256) k_bam_gather_wave(FqBamGatherArgs a) {
+  const uint32_t i = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (i < a.n) fq_bam_gather_record_lane(a, i, threadIdx.x & 63u);
+}
+int launch_bam_key(const FqBamKeyArgs &a) {
+  FQ_PRE();
+  if (!a.n) return 0;
+  hipEvent_t e0, e1;
+  kernel_events(FQ_KX_SORT, &e0, &e1);
+  hipExtLaunchKernelGGL(k_bam_key, dim3(nblk(a.n, 256)), dim3(256), 0, g_stream, e0, e1, 0, a);
+  FQ_HIP(hipGetLastError());
+  return 0;
+}
+int launch_sort_permute(const FqBamSortEnt *ent, const uint32_t *perm, uint32_t n, FqBamSortEnt *ent_out, uint32_t *len_out) {
+  FQ_PRE();
+  if (!n) return 0;
+  hipEvent_t e0, e1;
+  kernel_events(FQ_KX_SORT, &e0, &e1);
+  hipExtLaunchKernelGGL(k_sort_permute, dim3(nblk(n, 256)), dim3(256), 0, g_stream, e0, e1, 0, ent, perm, n, ent_out, len_out);
+  FQ_HIP(hipGetLastError());
+  return 0;
+}
+int launch_bam_gather(const FqBamGatherArgs &a) {
+  FQ_PRE();
+  if (!a.n || !a.total) return 0;
+  const uint64_t n = (a.total + 15) / 16;
+  hipEvent_t e0, e1;
+  kernel_events(FQ_KX_GATHER, &e0, &e1);
+  static const bool per_record = [] { const char *e = getenv("FASTQUICK_BAM_GATHER"); return !(e && !strcmp(e, "pieces")); }();      // a wavefront per record (measured: a third faster); A/B: pieces
+  if (per_record) hipExtLaunchKernelGGL(k_bam_gather_wave, dim3(nblk(a.n, 4)), dim3(256), 0, g_stream, e0, e1, 0, a);
+  else hipExtLaunchKernelGGL(k_bam_gather, dim3(nblk(n, 256)), dim3(256), 0, g_stream, e0, e1, 0, a, n);
+  FQ_HIP(hipGetLastError());
+  return 0;
+}
 __global__ void __launch_bounds__(256) k_qc_pair(FqQcArgs a, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) fq_qc_pair_thread(a, i);

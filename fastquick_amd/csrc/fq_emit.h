@@ -1010,3 +1010,10 @@ FQ_HD void fq_qc_base_record(const FqQcArgs &A, int idx, int lane, int nl, uint3
   }
 }
 enum { FQ_QOP_PAIR = 0, FQ_QOP_IST_FILL, FQ_QOP_PILE_FILL, FQ_QOP_BASE, FQ_QOP_COUNT };
+
+// ---- the coordinate order of BAM records (fq_sort.h; the sorted writer of fq_bam.cpp) ----
+// What `samtools sort` compares (bin/FASTQuick_template.sh:501 runs it on O.bam): the reference id as unsigned, the position, the strand.  tid is refID, or the
+// number of references when refID < 0 (records without a reference come last); pos + 1 counts as 0 below -1; rev is flag bit 0x10; pos_bits holds max LN + 1.
+FQ_HD uint64_t fq_bam_sort_key(uint32_t tid, int32_t pos, int rev, int pos_bits) {
+  return (uint64_t)tid << (pos_bits + 1) | (uint64_t)(pos < -1 ? 0 : pos + 1) << 1 | (uint64_t)(rev & 1);
+}

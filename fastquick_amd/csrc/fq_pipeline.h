@@ -174,10 +174,16 @@ struct FqQcCallOut {
 const FqQcCallOut *fq_ctx_qc_out(const fq_ctx_t *c);
 // ... and a call that formatted its BAM records on the device (fq_ctx_attach_bam): bytes in HBM, streamed off by the writer
 struct fq_bam;
-struct FqBamCallOut { const fq_bam *owner = nullptr; bool ready = false; uint64_t bytes = 0, z_bytes = 0; };   // z_bytes: the same records as finished BGZF members (0: not made)
+struct FqBamCallOut {
+  const fq_bam *owner = nullptr; bool ready = false; uint64_t bytes = 0, z_bytes = 0;   // z_bytes: the same records as finished BGZF members (0: not made)
+  bool sorted = false; uint64_t n_rec = 0; double sort_ms = 0, gather_ms = 0;      // (the kernel times of the run's keys + sort + permutation and of its gather, there after fq_ctx_emit_wait)
+  // sorted: a sorted writer's call (fq_sort.h): the records once more in key order and one FqBamSortEnt each, in HBM (fq_ctx_bam_stream: FQ_BAM_STREAM_*)
+};
+enum { FQ_BAM_STREAM_RECORDS = 0, FQ_BAM_STREAM_MEMBERS = 1, FQ_BAM_STREAM_SORTED = 2, FQ_BAM_STREAM_ENTRIES = 3 };
+bool fq_bam_sort_params(const fq_bam *b, int *n_ref, int *pos_bits, int *key_bits);   // false: not a sorted writer
 const FqBamCallOut *fq_ctx_bam_out(const fq_ctx_t *c);
 int fq_bam_device_prepare(fq_bam *b, FqBamArgs *a);
-int64_t fq_ctx_bam_stream(fq_ctx_t *c, fq_sink_fn sink, void *user, int members);   // members != 0: the BGZF members instead of the raw records
+int64_t fq_ctx_bam_stream(fq_ctx_t *c, fq_sink_fn sink, void *user, int what);   // what: FQ_BAM_STREAM_* (the raw records in input order, their BGZF members, a sorted call's records or entries)
 bool fq_bam_wants_members(const fq_bam *b);
 int fq_qc_device_prepare(fq_qc *q, FqQcArgs *a, int n_surv);
 // the counting steps of calls that share a consumer run one at a time, in the order in which the calls passed their order-dependent part

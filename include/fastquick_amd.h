@@ -448,6 +448,34 @@ int fq_ctx_attach_bam(fq_ctx_t *c, fq_bam_t *b);
  * block, CRC-32 -- csrc/fq_deflate.h), the members behind each other in out; replaces the zlib deflate of the reference's BGZF layer
  * (VerifyBamID/statgen/BgzfFileType.h over htslib's bgzf_write) for the records a context with a writer attached formats on the device. */
 int fq_bgzf_deflate_device(int device, const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int64_t *out_len, double *kernel_ms);
+/* ---- coordinate-sorted BAM with its index ----------------------------------------------------------------------------------
+ * Replaces the two steps the pipeline runs on O.bam before pop+con reads it (bin/FASTQuick_template.sh:501-502: `samtools sort -O BAM O.bam >
+ * O.sorted.bam`, `samtools index O.sorted.bam`).  The writer fq_bam_create_sorted returns takes records as every fq_bam_t does (fq_ctx_attach_bam,
+ * fq_bam_add_last, fq_bam_write_records) and keeps them as runs -- in host memory up to sort_mem_bytes, beyond that raw in bam_path + ".tmp.NNNN";
+ * fq_bam_close sorts all keys on the device (csrc/fq_sort.h: stable radix sort of (reference id, position, strand), ties in input order),
+ * writes the records in that order with "@HD\tVN:1.6\tSO:coordinate" in front of the header, and bam_path + ".bai" (SAM specification 5.2).
+ * The file holds the stable sort by that key of the records the unsorted writer would have written.  At most 2^32 - 1 records (FQ_ELIMIT).
+ * sort_mem_bytes bounds the record bytes held in memory only: every record also costs 16 bytes of entry and 8 of offset while the writer lives, and the close holds about
+ * 45 bytes more per record (keys, permutation, sorted entries, source and output offsets) -- some 9 GB for 134 M records, whatever sort_mem_bytes says. */
+int fq_bam_create_sorted(const fq_index_t *ix, const char *fai_path, const char *bam_path, const char *rg_line, const fq_qc_opts_t *o, int64_t sort_mem_bytes, fq_bam_t **out);
+typedef struct {
+  int64_t runs, device_sorted_runs, spilled_runs, records;   /* one run per fq_bam_add_last / fq_bam_write_records; device-sorted: ordered inside the call that made it */
+  int32_t key_bits, pos_bits;                                /* the key's width, from the .fai (replaces samtools sort's comparison: template.sh:501) */
+  double sort_kernel_ms;                                     /* entries, sort passes and permutation of the runs that attached contexts sorted inside their calls, plus the close's key sort (the scans between passes are not in it) */
+  double gather_kernel_ms;                                   /* the gather kernels of those runs; the close gathers on the host, so it adds nothing here */
+  double close_sec, close_sort_sec, close_assemble_sec, close_compress_sec, close_index_sec;   /* filled by fq_bam_close into the struct given to fq_bam_sort_stats_at_close */
+} fq_bam_sort_stats_t;
+/* what a sorted writer has taken so far (FQ_EINVAL for an unsorted one); replaces nothing in the reference -- samtools sort reports no such figures (template.sh:501) */
+int fq_bam_sort_stats(const fq_bam_t *b, fq_bam_sort_stats_t *out);
+/* fq_bam_close frees the writer: a struct registered here is filled in by the close with the final figures, the close's seconds included (template.sh:501-502) */
+int fq_bam_sort_stats_at_close(fq_bam_t *b, fq_bam_sort_stats_t *out);
+/* (tests, tools) the entries of run `run` of a sorted writer (run < 0: counted from the last), at most cap of them into out; returns how many the run has.
+ * One entry per record, in the order the run holds its records: the key samtools sort would compare (template.sh:501), the record's bytes, the alignment's end. */
+typedef struct { uint64_t key; uint32_t len; int32_t end; } fq_bam_sort_ent_t;
+int64_t fq_bam_sort_run_entries(const fq_bam_t *b, int64_t run, fq_bam_sort_ent_t *out, int64_t cap);
+/* (tests, tools) the stable order of n keys of key_bits bits by the device's sort (csrc/fq_sort.h): perm[i] = the place in `keys` of the i-th key in
+ * ascending order, equal keys in input order -- the comparison loop of samtools sort (template.sh:501) as a radix sort.  n < 2^32. */
+int fq_sort_keys_device(int device, const uint64_t *keys, int64_t n, int key_bits, uint32_t *perm, double *kernel_ms);
 
 /* ---- the consumers on the device ---------------------------------------------------------------
  * The reference hands every record to its consumers on its main thread, one after the other (src/BwtMapper.cpp:2030-2085): bwa_print_sam1
