@@ -93,7 +93,21 @@ class FrontEndStats(C.Structure):
     _fields_ = [("ms_inflate", C.c_double), ("ms_tokenise", C.c_double), ("members", C.c_int64), ("refused", C.c_int64),
                 ("text_bytes", C.c_int64), ("comp_bytes", C.c_int64), ("pairs", C.c_int64),
                 ("ms_lines", C.c_double), ("ms_records", C.c_double), ("ms_slots", C.c_double), ("inflate_launches", C.c_int64), ("chunks", C.c_int64),
-                ("ms_wait_reader", C.c_double), ("ms_wait_slot", C.c_double), ("ms_read", C.c_double), ("ms_upload", C.c_double)]
+                ("ms_wait_reader", C.c_double), ("ms_wait_slot", C.c_double), ("ms_read", C.c_double), ("ms_upload", C.c_double),
+                ("bam_records", C.c_int64), ("bam_skipped", C.c_int64), ("chain_repairs", C.c_int64), ("ms_transcode", C.c_double),
+                ("ms_bam_starts", C.c_double), ("ms_bam_pairs", C.c_double), ("ms_bam_fill", C.c_double)]
+
+
+class BamProbe(C.Structure):      # fq_bam_probe_t
+    _fields_ = [("n_ref", C.c_int32), ("paired", C.c_int32), ("first_flag", C.c_int32), ("first_l_seq", C.c_int32), ("first_l_name", C.c_int32), ("has_eof_block", C.c_int32),
+                ("header_bytes", C.c_int64), ("rec_member_off", C.c_int64), ("rec_off", C.c_int64), ("sort_order", C.c_char * 32), ("error", C.c_char * 256)]
+
+
+class BamTranscode(C.Structure):      # fq_bam_transcode_t
+    _fields_ = [("records", C.c_int64), ("kept", C.c_int64), ("units", C.c_int64), ("used_records", C.c_int64), ("text_len", C.c_int64 * 2),
+                ("chain_end", C.c_int64), ("carry_from", C.c_int64), ("bad_record", C.c_int64),
+                ("bad_kind", C.c_int32), ("paired", C.c_int32), ("chain_repairs", C.c_int32), ("end_flag", C.c_int32),
+                ("ms_starts", C.c_double), ("ms_pairs", C.c_double), ("ms_fill", C.c_double)]
 
 
 EXPORTS = ["fq_default_opts", "fq_index_build", "fq_index_load", "fq_index_destroy", "fq_index_l_pac",
@@ -105,7 +119,7 @@ EXPORTS = ["fq_default_opts", "fq_index_build", "fq_index_load", "fq_index_destr
            "fq_qc_add_last", "fq_qc_end_file", "fq_qc_write", "fq_qc_state_reset", "fq_qc_state_export", "fq_qc_merge", "fq_bam_create", "fq_bam_add_last", "fq_bam_format_last", "fq_bam_write_records", "fq_bam_close",
            "fq_fastq_open", "fq_fastq_configure", "fq_fastq_set_sampling", "fq_fastq_read", "fq_fastq_last_error", "fq_fastq_dropped_record", "fq_fastq_unequal_lengths", "fq_fastq_is_bgzf", "fq_fastq_close", "fq_inflate_raw", "fq_crc32", "fq_inflate_device", "fq_bgzf_inflate_device",
            "fq_frontend_open", "fq_frontend_next", "fq_frontend_release", "fq_frontend_handover", "fq_frontend_unequal_lengths", "fq_frontend_stats", "fq_frontend_last_error", "fq_frontend_close",
-           "fq_text_batch_pairs", "fq_text_batch_first_name", "fq_align_text", "fq_text_batch_fetch",
+           "fq_text_batch_pairs", "fq_text_batch_first_name", "fq_align_text", "fq_text_batch_fetch", "fq_bam_probe", "fq_frontend_open_bam", "fq_bam_transcode_device",
            "fq_ctx_set_emit", "fq_sam_device_last", "fq_sam_device_bytes", "fq_ctx_attach_qc", "fq_ctx_attach_bam", "fq_bgzf_deflate_device",
            "fq_bam_create_sorted", "fq_bam_sort_stats", "fq_bam_sort_stats_at_close", "fq_bam_sort_run_entries", "fq_sort_keys_device"]
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)
@@ -191,6 +205,10 @@ def load_library(path: str | None = None):
     L.fq_inflate_device.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                     C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_double)]
     L.fq_frontend_open.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    L.fq_frontend_open_bam.argtypes = [C.c_int, C.c_char_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    L.fq_bam_probe.argtypes = [C.c_char_p, C.POINTER(BamProbe)]
+    L.fq_bam_transcode_device.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                          C.c_void_p, C.c_int64, C.POINTER(BamTranscode)]
     L.fq_frontend_next.restype = C.c_int64
     L.fq_frontend_next.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.fq_frontend_release.restype = None
@@ -807,6 +825,42 @@ def bgzf_inflate_device(blob: bytes, text_cap: int, device: int = 0, lib=None, r
 
 
 FQ_EFALLBACK = -6
+BAM_BAD_KINDS = {0: None, 1: "mixed", 2: "l_seq0", 3: "fields", 4: "name", 5: "mates", 6: "names"}      # fq_bam_transcode_t::bad_kind
+
+
+def bam_probe(path: str, lib=None) -> dict:
+    """fq_bam_probe: the host's look at a BAM file (header, first kept record).  Raises FastquickError with the library's message."""
+    L = lib or load_library()
+    pr = BamProbe()
+    rc = L.fq_bam_probe(path.encode(), C.byref(pr))
+    if rc:
+        raise FastquickError(pr.error.decode(errors="replace") or "fq_bam_probe failed: %d" % rc)
+    d = {k: getattr(pr, k) for k, _ in BamProbe._fields_ if k not in ("error", "sort_order")}
+    d["sort_order"] = pr.sort_order.decode(errors="replace")
+    return d
+
+
+def bam_transcode_device(payload: bytes, member_off, n_ref: int, first_record: int = 0, paired: int = -1, device: int = 0, lib=None) -> dict:
+    """fq_bam_transcode_device: BAM records of a payload -> (text1, text2, record starts, counts, first refusal, chain_repairs); the members begin
+    at member_off (the cuts of the boundary search)."""
+    L = lib or load_library()
+    buf = np.frombuffer(bytes(payload) + b"\0", dtype=np.uint8)
+    n = len(payload)
+    mo = np.asarray(list(member_off), dtype=np.int64)
+    cap = 2 * n + 64
+    t1, t2 = np.zeros(cap, dtype=np.uint8), np.zeros(cap, dtype=np.uint8)
+    st = np.zeros(n // 36 + 2, dtype=np.uint32)
+    out = BamTranscode()
+    rc = L.fq_bam_transcode_device(device, buf.ctypes.data, n, mo.ctypes.data if mo.size else None, mo.size, n_ref, first_record, paired,
+                                   t1.ctypes.data, cap, t2.ctypes.data, cap, st.ctypes.data, st.size, C.byref(out))
+    if rc:
+        raise FastquickError("fq_bam_transcode_device failed: %d" % rc)
+    d = {k: getattr(out, k) for k, _ in BamTranscode._fields_ if k != "text_len"}
+    d["bad_kind"] = BAM_BAD_KINDS.get(out.bad_kind, out.bad_kind)
+    d["text1"] = t1[:out.text_len[0]].tobytes() if out.bad_record < 0 else None
+    d["text2"] = t2[:out.text_len[1]].tobytes() if out.bad_record < 0 else None
+    d["starts"] = [int(x) for x in st[:out.records]]
+    return d
 
 
 def stream_run(aligners, batches, n_calls, first=None, on_call=None, prefetch_beyond=False, lib=None):
@@ -847,10 +901,15 @@ class DeviceFrontEnd:
                  device: int = 0, lib=None):
         self.L = lib or load_library()
         self.h = C.c_void_p()
-        rc = self.L.fq_frontend_open(device, fq1.encode(), fq2.encode() if fq2 else None, batch_pairs, chunk_pairs, slot_mode, max_read_len, C.byref(self.h))
+        rc = self._open(device, fq1, fq2, batch_pairs, chunk_pairs, slot_mode, max_read_len)
         if rc:
-            raise FastquickError("fq_frontend_open failed: %d" % rc)
+            raise FastquickError("%s failed: %d" % (self._open_name, rc))
         self.batch_pairs, self.slot_mode = batch_pairs, slot_mode
+
+    _open_name = "fq_frontend_open"
+
+    def _open(self, device, fq1, fq2, batch_pairs, chunk_pairs, slot_mode, max_read_len):
+        return self.L.fq_frontend_open(device, fq1.encode(), fq2.encode() if fq2 else None, batch_pairs, chunk_pairs, slot_mode, max_read_len, C.byref(self.h))
 
     def next(self):
         b = C.c_void_p()
@@ -902,3 +961,16 @@ class DeviceFrontEnd:
         if self.h:
             self.L.fq_frontend_close(self.h)
             self.h = None
+
+
+class BamFrontEnd(DeviceFrontEnd):
+    """One BAM file through the front end on the device (fq_frontend_open_bam): the batches DeviceFrontEnd gives for the FASTQ texts its records
+    transcode to.  next() never returns FQ_EFALLBACK; what the contract refuses raises with the record's ordinal in the message."""
+    _open_name = "fq_frontend_open_bam"
+
+    def __init__(self, bam: str, batch_pairs: int = 262144, chunk_pairs: int = 16 * 262144, slot_mode: int = 0, max_read_len: int = 160, device: int = 0, lib=None):
+        bam_probe(bam, lib=lib)      # (its message, where the file is refused)
+        super().__init__(bam, None, batch_pairs, chunk_pairs, slot_mode, max_read_len, device, lib)
+
+    def _open(self, device, bam, _fq2, batch_pairs, chunk_pairs, slot_mode, max_read_len):
+        return self.L.fq_frontend_open_bam(device, bam.encode(), batch_pairs, chunk_pairs, slot_mode, max_read_len, C.byref(self.h))

@@ -8,6 +8,7 @@
 #include "fq_emit.h"
 #include "fq_deflate.h"
 #include "fq_sort.h"
+#include "fq_bamin.h"
 
 namespace fqdev {
 

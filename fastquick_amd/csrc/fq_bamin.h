@@ -1,0 +1,254 @@
+// fq_bamin.h -- BAM records in HBM -> the FASTQ text the front end's tokeniser takes (fq_frontend.h): the third part of `align --bam_in`, behind
+// the BGZF member decoder and in front of the line index.  The reference interface this stands in for is the dormant bwa_read_bam
+// (libbwa/bwaseqio.c:90-142, switched off at src/BwtMapper.cpp:185-187): name, bases from the 4-bit codes, quality + 33 capped at 126, reverse
+// strand records turned back (bwaseqio.c:103-129); where it says nothing -- which records are kept, how mates are found -- the common default of
+// `samtools fastq` on collated input.  The per-item bodies below are stated once: fq_device.hip wraps them in kernels, and a build without hipcc
+// (tests/emu) gets the launchers as host loops over the same bodies, defined inline here.
+//
+//   (a) record starts   Record boundaries are a chain of block_size fields, serial by format.  The chain is cut at the BGZF members (<= 64 KiB of
+//                       payload each): a wavefront per member looks for the member's first record -- 64 candidate offsets a step against
+//                       fq_bam_plausible, first hit by ballot -- and walks on from there, counting.  The guess is then VERIFIED on the host over
+//                       16 bytes per member: member k's walk is the chain's only if it began where the chain enters k; where it did not, k is walked
+//                       again from the true offset (a repair), and members the chain jumps over hold no start whatever they guessed.  The result
+//                       is exactly the chain from the first record behind the header: a wrong guess costs a relaunch, never a record.  Past
+//                       FQB_MAX_REPAIRS relaunches one thread walks the rest.  One scan over the counts, and a second pass writes the starts.
+//   (b) keep, pair      a thread per record: kept unless secondary / supplementary; a scan ranks the kept; a thread per pair (per record of a
+//                       single-end stream) checks flags and names, says which record goes to which side and how long its text is
+//   (c) fill            a wavefront per (pair, side): the four lines, a dword of destination a lane and step
+#pragma once
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "fq_kernels.h"
+
+#define FQB_NONE 0xffffffffu
+#define FQB_MAX_BLOCK (1u << 28)          // a block_size (or l_seq) above this is not a record's
+#define FQB_MAX_REPAIRS 64                // relaunches of a member's walk in one chunk; then the serial walk
+enum { FQB_SEG_OK = 0, FQB_SEG_CUT = 1, FQB_SEG_CORRUPT = 2 };      // how a member's walk ended: at the member's end; at a record the payload's end cuts off; at a block_size that is none
+// what a record is refused for; a refusal is the pair (record ordinal, kind) as ordinal << 3 | kind, and the stream's is the smallest
+enum { FQB_BAD_MIXED = 1, FQB_BAD_LSEQ0 = 2, FQB_BAD_FIELDS = 3, FQB_BAD_NAME = 4, FQB_BAD_MATES = 5, FQB_BAD_NAMES = 6 };
+#define FQB_NO_BAD 0xffffffffffffffffull
+
+// seg[0 .. n_seg]: where the members begin in the payload (seg[0]: the first record; seg[n_seg] = n); per member: first (where its walk began, or
+// FQB_NONE), last_next (the offset behind its last record), count, flag
+struct FqBamChainArgs {
+  const uint8_t *pay; uint32_t n; const uint32_t *seg; uint32_t n_seg; int32_t n_ref;
+  uint32_t *first, *last_next, *count, *flag;
+  const uint64_t *base; uint32_t *starts;       // (second pass) base[k]: the records in front of member k
+};
+struct FqBamPairArgs {
+  const uint8_t *pay; const uint32_t *starts; uint32_t n_rec;
+  uint32_t *kept; const uint64_t *kord; uint32_t *kidx;        // kept[i] 0/1, its scan, the kept records' indices
+  uint32_t n_units; int32_t paired; uint64_t ord0;             // units: pairs, or single records; ord0: the stream's records in front of this chunk's
+  uint32_t *src[2], *len[2];                                   // per unit and side: the record's offset, its text's length
+  uint64_t *bad;
+};
+struct FqBamFillArgs { const uint8_t *pay; const uint32_t *src[2]; const uint64_t *off[2]; uint8_t *text[2]; uint32_t n_units; int32_t n_sides; uint64_t total[2]; };      // total[e] = off[e][n_units]
+
+FQ_HD uint32_t fqb_ld16(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
+FQ_HD uint32_t fqb_ld32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+// what block_size must cover: the fixed fields, the name, the CIGAR, the packed bases and the qualities
+FQ_HD uint64_t fqb_min_block(uint32_t l_name, uint32_t n_cig, uint32_t l_seq) { return 32ull + l_name + 4ull * n_cig + ((uint64_t)l_seq + 1) / 2 + l_seq; }
+
+// ---- (a) ----
+// Could a record begin at c?  Its fixed fields against its block_size; false too when fewer than 36 bytes are left.  *next: where it ends.
+FQ_HD bool fq_bam_plausible1(const uint8_t *pay, uint32_t n, uint64_t c, int32_t n_ref, uint64_t *next) {
+  if (c + 36 > n) return false;
+  const uint8_t *r = pay + c;
+  const uint32_t bs = fqb_ld32(r), l_name = r[12], n_cig = fqb_ld16(r + 16), l_seq = fqb_ld32(r + 20);
+  const int32_t ref = (int32_t)fqb_ld32(r + 4), nref = (int32_t)fqb_ld32(r + 24);
+  if (bs > FQB_MAX_BLOCK || l_seq > FQB_MAX_BLOCK || bs < fqb_min_block(l_name, n_cig, l_seq)) return false;
+  if (ref < -1 || ref >= n_ref || nref < -1 || nref >= n_ref) return false;
+  if (l_name < 2) return false;
+  const uint64_t nul = c + 36 + l_name - 1;
+  if (nul < n && pay[nul] != 0) return false;
+  *next = c + 4 + bs;
+  return true;
+}
+// ... and the two records behind it, as far as the payload shows their fixed fields
+FQ_HD bool fq_bam_plausible(const uint8_t *pay, uint32_t n, uint32_t c, int32_t n_ref) {
+  uint64_t p = c, nx = 0;
+  if (!fq_bam_plausible1(pay, n, p, n_ref, &nx)) return false;
+  for (int d = 0; d < 2; ++d) {
+    p = nx;
+    if (p + 36 > n) return true;
+    if (!fq_bam_plausible1(pay, n, p, n_ref, &nx)) return false;
+  }
+  return true;
+}
+// The records that begin in member k, from p on (seg[k] <= p): counted, and written to out when it is given.  Every step moves on by 36 bytes at
+// least and stays inside the payload, whatever the bytes say.
+FQ_HD void fq_bam_walk_seg(const FqBamChainArgs &a, uint32_t k, uint32_t p, uint32_t *out) {
+  const uint32_t end = a.seg[k + 1], p0 = p;
+  uint32_t cnt = 0, flag = FQB_SEG_OK;
+  while (p < end) {
+    if ((uint64_t)p + 4 > a.n) { flag = FQB_SEG_CUT; break; }
+    const uint32_t bs = fqb_ld32(a.pay + p);
+    if (bs < 32 || bs > FQB_MAX_BLOCK) { flag = FQB_SEG_CORRUPT; break; }
+    if ((uint64_t)p + 4 + bs > a.n) { flag = FQB_SEG_CUT; break; }
+    if (out) out[cnt] = p;
+    ++cnt; p += 4 + bs;
+  }
+  if (!out) { a.first[k] = p0; a.last_next[k] = p; a.count[k] = cnt; a.flag[k] = flag; }
+}
+FQ_HD void fq_bam_seg_none(const FqBamChainArgs &a, uint32_t k) { a.first[k] = FQB_NONE; a.last_next[k] = FQB_NONE; a.count[k] = 0; a.flag[k] = FQB_SEG_OK; }
+// second pass, a thread per member: the starts of its records at their places
+FQ_HD void fq_bam_starts_thread(const FqBamChainArgs &a, uint32_t k) {
+  if (a.count[k]) fq_bam_walk_seg(a, k, a.first[k], a.starts + a.base[k]);
+}
+// the chain from p (in member k) to the payload's end on one thread: what the members' guesses are held to, and what is left when too many were wrong
+FQ_HD void fq_bam_chain_serial(const FqBamChainArgs &a, uint32_t k, uint32_t p) {
+  while (k < a.n_seg) {
+    fq_bam_walk_seg(a, k, p, nullptr);
+    p = a.last_next[k];
+    const bool ended = a.flag[k] != FQB_SEG_OK || p >= a.n;
+    ++k;
+    while (k < a.n_seg && (ended || a.seg[k + 1] <= p)) { fq_bam_seg_none(a, k); ++k; }
+  }
+}
+
+// ---- (b) ----
+FQ_HD void fq_bam_keep_thread(const FqBamPairArgs &a, uint32_t i) { a.kept[i] = (fqb_ld16(a.pay + a.starts[i] + 18) & 0x900u) ? 0u : 1u; }
+FQ_HD void fq_bam_kidx_thread(const FqBamPairArgs &a, uint32_t i) { if (a.kept[i]) a.kidx[a.kord[i]] = i; }
+FQ_HD uint64_t fqb_bad(uint64_t ord, uint32_t kind) { return ord << 3 | kind; }
+FQ_HD uint64_t fqb_min64(uint64_t x, uint64_t y) { return x < y ? x : y; }
+// what one kept record is refused for on its own (FQB_NO_BAD: nothing)
+FQ_HD uint64_t fq_bam_record_check(const uint8_t *r, uint64_t ord, int32_t paired) {
+  const uint32_t bs = fqb_ld32(r), l_name = r[12], n_cig = fqb_ld16(r + 16), flag = fqb_ld16(r + 18), l_seq = fqb_ld32(r + 20);
+  if (((flag & 1u) != 0) != (paired != 0)) return fqb_bad(ord, FQB_BAD_MIXED);
+  if (l_seq == 0) return fqb_bad(ord, FQB_BAD_LSEQ0);
+  if (l_seq > FQB_MAX_BLOCK || bs < fqb_min_block(l_name, n_cig, l_seq)) return fqb_bad(ord, FQB_BAD_FIELDS);      // (the fill reads name, bases and qualities inside the record only)
+  if (l_name < 2) return fqb_bad(ord, FQB_BAD_NAME);
+  for (uint32_t j = 0; j + 1 < l_name; ++j) if (r[36 + j] < 0x21 || r[36 + j] > 0x7e) return fqb_bad(ord, FQB_BAD_NAME);
+  return FQB_NO_BAD;
+}
+FQ_HD uint32_t fq_bam_text_len(const uint8_t *r) { return (uint32_t)r[12] - 1u + 2u * fqb_ld32(r + 20) + 6u; }
+// a pair (kept records 2u, 2u + 1) or a single-end record: its refusal, or FQB_NO_BAD
+FQ_HD uint64_t fq_bam_unit_thread(const FqBamPairArgs &a, uint32_t u) {
+  if (!a.paired) {
+    const uint32_t i = a.kidx[u], s = a.starts[i];
+    const uint64_t bad = fq_bam_record_check(a.pay + s, a.ord0 + i, 0);
+    a.src[0][u] = s; a.len[0][u] = bad == FQB_NO_BAD ? fq_bam_text_len(a.pay + s) : 0;
+    return bad;
+  }
+  const uint32_t ia = a.kidx[2 * u], ib = a.kidx[2 * u + 1], sa = a.starts[ia], sb = a.starts[ib];
+  const uint8_t *ra = a.pay + sa, *rb = a.pay + sb;
+  uint64_t bad = fqb_min64(fq_bam_record_check(ra, a.ord0 + ia, 1), fq_bam_record_check(rb, a.ord0 + ib, 1));
+  const uint32_t fa = fqb_ld16(ra + 18) & 0xc0u, fb = fqb_ld16(rb + 18) & 0xc0u;
+  const bool a_first = fa == 0x40u && fb == 0x80u;
+  if (bad == FQB_NO_BAD && !a_first && !(fa == 0x80u && fb == 0x40u)) bad = fqb_bad(a.ord0 + ia, FQB_BAD_MATES);      // (two records that stand on their own: are they a pair?)
+  if (bad == FQB_NO_BAD) {
+    bool same = ra[12] == rb[12];
+    for (uint32_t j = 0; same && j < ra[12]; ++j) same = ra[36 + j] == rb[36 + j];
+    if (!same) bad = fqb_bad(a.ord0 + ia, FQB_BAD_NAMES);
+  }
+  a.src[0][u] = a_first ? sa : sb; a.src[1][u] = a_first ? sb : sa;
+  a.len[0][u] = bad == FQB_NO_BAD ? fq_bam_text_len(a_first ? ra : rb) : 0;
+  a.len[1][u] = bad == FQB_NO_BAD ? fq_bam_text_len(a_first ? rb : ra) : 0;
+  return bad;
+}
+
+// ---- (c) ----
+// byte j of the record's four lines "@name\nSEQ\n+\nQUAL\n" (nm name bytes, l bases)
+FQ_HD uint8_t fq_bam_text_byte(const uint8_t *r, uint32_t nm, uint32_t l, uint32_t n_cig, bool rev, uint32_t j) {
+  if (j == 0) return '@';
+  if (j <= nm) return r[36 + j - 1];
+  j -= nm + 1;
+  if (j == 0) return '\n';
+  const uint8_t *seq = r + 36 + nm + 1 + 4 * n_cig;
+  if (j <= l) {
+    const uint32_t b = rev ? l - j : j - 1;
+    const uint32_t code = (seq[b >> 1] >> ((~b & 1u) << 2)) & 15u;
+    return (uint8_t)(rev ? "=TGKCYSBAWRDMHVN" : "=ACMGRSVTWYHKDBN")[code];
+  }
+  j -= l + 1;
+  if (j == 0) return '\n';
+  if (j == 1) return '+';
+  if (j == 2) return '\n';
+  j -= 3;
+  if (j < l) {
+    const uint32_t q = (seq + (l + 1) / 2)[rev ? l - 1 - j : j];
+    return (uint8_t)(q > 93u ? 126u : q + 33u);        // min(q + 33, 126) (bwaseqio.c:118); a missing quality (0xff) is '~' as well
+  }
+  return '\n';
+}
+// lane of the wavefront of (unit u, side e).  The text lies at any alignment: a lane takes an aligned dword of the destination a step, whole dwords
+// inside the record's text are stored as dwords (256 contiguous bytes a wavefront and step), the at most three bytes at either end as bytes.
+FQ_HD void fq_bam_fill_lane(const FqBamFillArgs &a, uint32_t u, int e, uint32_t lane) {
+  const uint8_t *r = a.pay + a.src[e][u];
+  const uint32_t nm = (uint32_t)r[12] - 1u, n_cig = fqb_ld16(r + 16), l = fqb_ld32(r + 20);
+  const bool rev = (fqb_ld16(r + 18) & 0x10u) != 0;
+  const uint64_t len = a.off[e][u + 1] - a.off[e][u];
+  uint8_t *d = a.text[e] + a.off[e][u];
+  const uint32_t mis = (uint32_t)((uintptr_t)d & 3u);
+  for (uint64_t w = lane;; w += 64) {
+    const int64_t j0 = (int64_t)(4 * w) - (int64_t)mis;
+    if (j0 >= (int64_t)len) break;
+    if (j0 >= 0 && (uint64_t)j0 + 4 <= len) {
+      uint32_t v = 0;
+      for (uint32_t t = 0; t < 4; ++t) v |= (uint32_t)fq_bam_text_byte(r, nm, l, n_cig, rev, (uint32_t)j0 + t) << (8 * t);
+      *(uint32_t *)(d + j0) = v;
+    } else {
+      for (int64_t j = j0 < 0 ? 0 : j0; j < j0 + 4 && j < (int64_t)len; ++j) d[j] = fq_bam_text_byte(r, nm, l, n_cig, rev, (uint32_t)j);
+    }
+  }
+}
+// The other form (A/B, FASTQUICK_BAM_FILL=pieces): a thread per sixteen aligned destination bytes of side e, as fq_sort.h's fq_bam_gather_piece16 -- the unit
+// that holds the piece's first byte by bisection over off[e], then on through the units; a whole piece inside the text is stored as four dwords.
+FQ_HD void fq_bam_fill_piece(const FqBamFillArgs &a, int e, uint64_t t) {
+  const uint32_t mis = (uint32_t)((uintptr_t)a.text[e] & 15u);
+  const int64_t lo_b = (int64_t)(16 * t) - (int64_t)mis;                    // text offsets [lo_b, lo_b + 16) cut to [0, total)
+  uint64_t b = lo_b < 0 ? 0 : (uint64_t)lo_b;
+  const uint64_t hi = (uint64_t)(lo_b + 16) < a.total[e] ? (uint64_t)(lo_b + 16) : a.total[e];
+  if (lo_b + 16 <= 0 || b >= hi) return;
+  uint32_t lo = 0, up = a.n_units;                                          // the last unit with off <= b
+  while (up - lo > 1) { const uint32_t m = lo + ((up - lo) >> 1); if (a.off[e][m] <= b) lo = m; else up = m; }
+  uint32_t u = lo, w[4] = {0, 0, 0, 0};
+  const bool whole = lo_b >= 0 && hi == (uint64_t)lo_b + 16;
+  while (b < hi) {
+    while (u + 1 < a.n_units && a.off[e][u + 1] <= b) ++u;
+    const uint64_t uend = a.off[e][u + 1] < hi ? a.off[e][u + 1] : hi;
+    const uint8_t *r = a.pay + a.src[e][u];
+    const uint32_t nm = (uint32_t)r[12] - 1u, n_cig = fqb_ld16(r + 16), l = fqb_ld32(r + 20);
+    const bool rev = (fqb_ld16(r + 18) & 0x10u) != 0;
+    for (; b < uend; ++b) {
+      const uint8_t c = fq_bam_text_byte(r, nm, l, n_cig, rev, (uint32_t)(b - a.off[e][u]));
+      if (whole) { const uint32_t k = (uint32_t)(b - (uint64_t)lo_b); w[k >> 2] |= (uint32_t)c << (8 * (k & 3)); } else a.text[e][b] = c;
+    }
+  }
+  if (whole) { uint32_t *d = (uint32_t *)(a.text[e] + lo_b); d[0] = w[0]; d[1] = w[1]; d[2] = w[2]; d[3] = w[3]; }
+}
+FQ_HD uint64_t fq_bam_fill_pieces(const FqBamFillArgs &a, int e) { return a.total[e] ? (a.total[e] + ((uintptr_t)a.text[e] & 15u) + 15) / 16 : 0; }
+
+namespace fqdev {
+#if defined(__HIPCC__)
+int launch_bam_guess(const FqBamChainArgs &a);                                  // a wavefront per member: first / last_next / count / flag
+int launch_bam_rewalk(const FqBamChainArgs &a, uint32_t k, uint32_t p, int to_end);   // one thread: member k from p (to_end: the chain from there to the payload's end)
+int launch_bam_starts(const FqBamChainArgs &a);                                 // a thread per member
+int launch_bam_keep(const FqBamPairArgs &a);                                    // a thread per record
+int launch_bam_kidx(const FqBamPairArgs &a);
+int launch_bam_units(const FqBamPairArgs &a);                                   // a thread per pair; *a.bad lowered to the first refusal
+int launch_bam_fill(const FqBamFillArgs &a);                                    // a wavefront per (pair, side) (FASTQUICK_BAM_FILL=pieces: a thread per sixteen destination bytes, A/B)
+#else
+inline int launch_bam_guess(const FqBamChainArgs &a) {
+  for (uint32_t k = 0; k < a.n_seg; ++k) {
+    uint32_t c = a.seg[k];
+    if (k) { while (c < a.seg[k + 1] && !fq_bam_plausible(a.pay, a.n, c, a.n_ref)) ++c; }
+    if (c < a.seg[k + 1]) fq_bam_walk_seg(a, k, c, nullptr); else fq_bam_seg_none(a, k);
+  }
+  return 0;
+}
+inline int launch_bam_rewalk(const FqBamChainArgs &a, uint32_t k, uint32_t p, int to_end) { if (to_end) fq_bam_chain_serial(a, k, p); else fq_bam_walk_seg(a, k, p, nullptr); return 0; }
+inline int launch_bam_starts(const FqBamChainArgs &a) { for (uint32_t k = 0; k < a.n_seg; ++k) fq_bam_starts_thread(a, k); return 0; }
+inline int launch_bam_keep(const FqBamPairArgs &a) { for (uint32_t i = 0; i < a.n_rec; ++i) fq_bam_keep_thread(a, i); return 0; }
+inline int launch_bam_kidx(const FqBamPairArgs &a) { for (uint32_t i = 0; i < a.n_rec; ++i) fq_bam_kidx_thread(a, i); return 0; }
+inline int launch_bam_units(const FqBamPairArgs &a) { for (uint32_t u = 0; u < a.n_units; ++u) *a.bad = fqb_min64(*a.bad, fq_bam_unit_thread(a, u)); return 0; }
+inline int launch_bam_fill(const FqBamFillArgs &a) {      // (the variable is read at every call here, so that one test process holds either body to the texts)
+  const char *form = getenv("FASTQUICK_BAM_FILL");
+  if (form && !strcmp(form, "pieces")) { for (int e = 0; e < a.n_sides; ++e) for (uint64_t t = 0; t < fq_bam_fill_pieces(a, e); ++t) fq_bam_fill_piece(a, e, t); return 0; }
+  for (uint32_t u = 0; u < a.n_units; ++u) for (int e = 0; e < a.n_sides; ++e) for (uint32_t lane = 0; lane < 64; ++lane) fq_bam_fill_lane(a, u, e, lane);
+  return 0;
+}
+#endif
+}  // namespace fqdev

@@ -101,6 +101,8 @@ struct Args {
   bool host_consumers = false;   // --host_consumers: SAM text and StatCollector's sums on the host's threads from the result arrays (round 5's way; the default runs them in kernels, fq_emit.h)
   bool host_reader = false;   // --host_reader: the FASTQ front end on the host's threads also for BGZF files (the default inflates and tokenises them on the device)
   bool strict = false;   // --strict_reference: stop where the output could differ from the reference's bytes (today: QUAL of reads of unequal lengths)
+  std::string bam_in;         // --bam_in: one BAM file in place of the FASTQ files (fq_frontend_open_bam: its records are transcoded to FASTQ text on the device)
+  int bam_l_seq = 0;          // ... the first kept record's length (fq_bam_probe): sizes the rows as a FASTQ file's first record does
   std::string fq_list, rg = "@RG\\tID:foo\\tSM:bar";   // runAlign's default --RG (src/FASTQuick.cpp:170)
   bool cal_dup = true;
   double frac = 1.0;    // --frac_samp: gap_opt_t::frac (libbwa/bwtaln.c:47), the share of the records that is kept
@@ -108,7 +110,7 @@ struct Args {
 };
 
 int usage() {
-  fprintf(stderr, "Usage: FASTQuick_amd align --index_prefix P --fastq_1 R1.fq[.gz] [--fastq_2 R2.fq[.gz]] | --fq_list LIST  --out_prefix O [--sam_out | --sorted_bam [--sort_mem BYTES]] [--RG STR] [--cal_dup]\n"
+  fprintf(stderr, "Usage: FASTQuick_amd align --index_prefix P --fastq_1 R1.fq[.gz] [--fastq_2 R2.fq[.gz]] | --fq_list LIST | --bam_in X.bam  --out_prefix O [--sam_out | --sorted_bam [--sort_mem BYTES]] [--RG STR] [--cal_dup]\n"
                   "                       [--q INT] [--n FLOAT|INT] [--kmer_thresh INT] [--o INT] [--e INT] [--i INT] [--d INT] [--l INT] [--k INT]\n"
                   "                       [--m INT] [--R INT] [--N] [--L] [--I] [--max_isize INT] [--max_occ INT] [--is_sw] [--n_multi INT] [--N_multi INT]\n"
                   "                       [--ap_prior FLOAT] [--force_isize] [--frac_samp FLOAT] [--t INT] [--chunk_pairs INT] [--batch_pairs INT] [--device INT | --devices LIST] [--read_len INT] [--clean_names] [--strict_reference] [--host_reader] [--host_consumers]\n"
@@ -126,7 +128,8 @@ const int kNameStride = 304;   // the reference's name buffers hold 302 bytes (b
 int row_stride(const Args &A, const std::string &fq1, const std::string &fq2) {
   auto regular = [](const std::string &p) { struct stat s; return stat(p.c_str(), &s) == 0 && S_ISREG(s.st_mode); };
   size_t l = 0;
-  if (regular(fq1) && (fq2.empty() || regular(fq2))) l = std::max(first_read_len(fq1), fq2.empty() ? (size_t)0 : first_read_len(fq2));
+  if (!A.bam_in.empty()) l = (size_t)A.bam_l_seq;
+  else if (regular(fq1) && (fq2.empty() || regular(fq2))) l = std::max(first_read_len(fq1), fq2.empty() ? (size_t)0 : first_read_len(fq2));
   return (int)((std::max<size_t>(l, (size_t)std::max(A.read_len, 16)) + 15) & ~(size_t)15);
 }
 
@@ -347,6 +350,12 @@ void unequal_lengths_notice(const Args &A, const fq_fastq_t *a, const fq_fastq_t
 fq_frontend_t *open_device_front_end(const Args &A, const std::string &f1, const std::string &f2, int device, int slot_mode, int stride) {
   if (A.host_reader || A.frac < 1.0) return nullptr;       // (--frac_samp: the reference's generator is walked record by record, on the host)
   fq_frontend_t *fe = nullptr;
+  if (!A.bam_in.empty()) {
+    const int rc = fq_frontend_open_bam(device, A.bam_in.c_str(), A.o.batch_pairs, A.chunk_pairs, slot_mode, stride, &fe);
+    mark("front end open");
+    if (rc) die("--bam_in: cannot start the front end on device " + std::to_string(device) + " for " + A.bam_in + " (" + std::to_string(rc) + ")");
+    return fe;
+  }
   const int rc = fq_frontend_open(device, f1.c_str(), f2.empty() ? nullptr : f2.c_str(), A.o.batch_pairs, A.chunk_pairs, slot_mode, stride, &fe);
   mark("front end open");
   if (rc == FQ_EIO) return nullptr;                          // not a regular BGZF file: the host reader's
@@ -358,6 +367,9 @@ void front_end_notice(fq_frontend_t *fe) {
   fq_frontend_stats(fe, &st);
   fprintf(stderr, "NOTICE - front end on the device: %lld pairs, %lld BGZF members (%lld left to the host's decoder), %.1f MB -> %.1f MB of text; inflate %.1f ms ; lines, records, keys, slots %.1f ms\n",
           (long long)st.pairs, (long long)st.members, (long long)st.refused, 1e-6 * (double)st.comp_bytes, 1e-6 * (double)st.text_bytes, st.ms_inflate, st.ms_tokenise);
+  if (st.bam_records || st.ms_transcode > 0)
+    fprintf(stderr, "NOTICE - BAM input on the device: %lld records (%lld skipped as secondary or supplementary), %lld repairs of the record chain; records -> text %.1f ms (starts %.1f, pairs %.1f, fill %.1f)\n",
+            (long long)st.bam_records, (long long)st.bam_skipped, (long long)st.chain_repairs, st.ms_transcode, st.ms_bam_starts, st.ms_bam_pairs, st.ms_bam_fill);
 }
 
 
@@ -741,10 +753,25 @@ struct Run {
   std::vector<Worker> wk;
   std::string worker_prefix(size_t w) const { return A.out_prefix + ".worker" + std::to_string(w); }
 };
+// --bam_in: what it cannot be combined with, and the host's look at the file (fq_bam_probe): paired or single-end, the rows' width
+bool probe_bam_input(Args &A) {
+  // BAM input runs through the device front end alone: the flags below take host FASTQ readers, or shard over them (a host-side BAM reader is not built)
+  if (!A.fq1.empty() || !A.fq2.empty()) die("--bam_in is an input of its own: it cannot be combined with --fastq_1 / --fastq_2");
+  if (!A.fq_list.empty()) die("--bam_in cannot be combined with --fq_list (a list of BAM files is not supported)");
+  if (A.host_reader) die("--bam_in cannot be combined with --host_reader (BAM records are read on the device only)");
+  if (A.frac < 1.0) die("--bam_in cannot be combined with --frac_samp below 1 (sampling walks the records on the host)");
+  if (!A.devices.empty() && parse_devices(A.devices).size() > 1) die("--bam_in cannot be combined with --devices naming more than one device (sharding takes host readers)");
+  fq_bam_probe_t pr;
+  if (fq_bam_probe(A.bam_in.c_str(), &pr)) die(std::string("--bam_in: ") + pr.error);
+  A.bam_l_seq = pr.first_l_seq;
+  if (!strcmp(pr.sort_order, "coordinate")) fprintf(stderr, "NOTICE - %s says SO:coordinate: mates must be adjacent (collate the file by name first)\n", A.bam_in.c_str());
+  return pr.paired != 0;
+}
 // --fq_list: one FASTQ pair per line, '#' lines skipped (src/BwtMapper.cpp:232-262); every pair is an independent stream
 // (its own srand48, last_ii, position cache and read slots: PairEndMapper sets them up per call), all into one output
-std::vector<std::pair<std::string, std::string>> read_inputs(const Args &A) {
+std::vector<std::pair<std::string, std::string>> read_inputs(const Args &A, bool bam_paired) {
   std::vector<std::pair<std::string, std::string>> inputs;
+  if (!A.bam_in.empty()) { inputs.emplace_back(A.bam_in, bam_paired ? A.bam_in : ""); return inputs; }
   if (A.fq_list.empty()) {
     if (A.fq1.empty()) die("--fastq_1 (and --fastq_2 for paired-end reads), or --fq_list, is required");
     inputs.emplace_back(A.fq1, A.fq2);
@@ -1023,7 +1050,7 @@ int main(int argc, char **argv) {
     else if (f == "--RG") A.rg = need("");
     else if (f == "--cal_dup") A.cal_dup = !A.cal_dup;        // (a bool flag on a default-1 field, like --is_sw)
     else if (f == "--frac_samp") A.frac = atof(need(""));
-    else if (f == "--bam_in") die(f + " is not supported (the reference's BAM input is disabled, too)");
+    else if (f == "--bam_in") A.bam_in = need("");
     else die("unknown option " + f);
   }
   if (A.o.fnr >= 1.0) { A.o.max_diff = (int)A.o.fnr; A.o.fnr = -1.0; }                  // src/FASTQuick.cpp:312-315
@@ -1035,7 +1062,7 @@ int main(int argc, char **argv) {
   if (A.sorted_bam && A.sam_out) die("--sorted_bam writes a BAM file: it cannot be combined with --sam_out (sorting the SAM text is not supported)");
   if (A.out_prefix == "Empty") die("--out_prefix is required");
   if (A.index_prefix == "Empty") die("--index_prefix is required");
-  R.inputs = read_inputs(A);
+  R.inputs = read_inputs(A, !A.bam_in.empty() && probe_bam_input(A));
   if (A.o.batch_pairs < 1) die("--batch_pairs must be positive");
   A.chunk_pairs = std::max<long long>(A.o.batch_pairs, A.chunk_pairs / A.o.batch_pairs * A.o.batch_pairs);   // whole reference batches per chunk
 

@@ -1823,6 +1823,115 @@ int launch_aln_index(const int32_t *work, const uint32_t *status, const uint64_t
   return 0;
 }
 
+// ---- BAM input (fq_bamin.h): record starts, keep / pair / measure, fill ----
+__global__ void __launch_bounds__(256) k_bam_guess(FqBamChainArgs a) {
+  const uint32_t k = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (k >= a.n_seg) return;                 // (a whole wavefront)
+  const uint32_t s = a.seg[k], e = a.seg[k + 1];
+  uint32_t first = FQB_NONE;
+  if (k == 0) first = s < e ? s : FQB_NONE;      // the chain's own first record
+  else
+    for (uint32_t c0 = s; c0 < e; c0 += 64) {
+      const uint32_t c = c0 + lane;
+      const unsigned long long hit = __ballot(c < e && fq_bam_plausible(a.pay, a.n, c, a.n_ref));
+      if (hit) { first = c0 + (uint32_t)(__ffsll((long long)hit) - 1); break; }
+    }
+  if (lane == 0) { if (first != FQB_NONE) fq_bam_walk_seg(a, k, first, nullptr); else fq_bam_seg_none(a, k); }
+}
+__global__ void k_bam_rewalk(FqBamChainArgs a, uint32_t k, uint32_t p, int to_end) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) { if (to_end) fq_bam_chain_serial(a, k, p); else fq_bam_walk_seg(a, k, p, nullptr); }
+}
+__global__ void __launch_bounds__(256) k_bam_starts(FqBamChainArgs a) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < a.n_seg) fq_bam_starts_thread(a, k);
+}
+__global__ void __launch_bounds__(256) k_bam_keep(FqBamPairArgs a) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < a.n_rec) fq_bam_keep_thread(a, i);
+}
+__global__ void __launch_bounds__(256) k_bam_kidx(FqBamPairArgs a) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < a.n_rec) fq_bam_kidx_thread(a, i);
+}
+// the first refusal: folded over the wavefront, committed by one lane and only where it lowers the value (a look first, as FQF_ATOMIC_MIN32)
+__global__ void __launch_bounds__(256) k_bam_units(FqBamPairArgs a) {
+  const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
+  uint64_t bad = u < a.n_units ? fq_bam_unit_thread(a, u) : FQB_NO_BAD;
+  for (int d = 32; d >= 1; d >>= 1) {
+    const uint64_t o = (uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)bad, d, 64) | (uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(bad >> 32), d, 64) << 32;
+    bad = o < bad ? o : bad;
+  }
+  if ((threadIdx.x & 63u) == 0 && bad != FQB_NO_BAD && bad < __hip_atomic_load((const unsigned long long *)a.bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+    atomicMin((unsigned long long *)a.bad, (unsigned long long)bad);
+}
+__global__ void __launch_bounds__(256) k_bam_fill(FqBamFillArgs a) {
+  const uint64_t w = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+  const uint32_t u = (uint32_t)(w / (uint32_t)a.n_sides);
+  if (u < a.n_units) fq_bam_fill_lane(a, u, (int)(w % (uint32_t)a.n_sides), threadIdx.x & 63u);
+}
+int launch_bam_guess(const FqBamChainArgs &a) {
+  FQ_PRE();
+  if (!a.n_seg) return 0;
+  hipLaunchKernelGGL(k_bam_guess, dim3(nblk(a.n_seg, 4)), dim3(256), 0, g_stream, a);
+  FQ_HIP(hipGetLastError());
+  return 0;
+}
+int launch_bam_rewalk(const FqBamChainArgs &a, uint32_t k, uint32_t p, int to_end) {
+  FQ_PRE();
+  if (k >= a.n_seg) return 0;
+  hipLaunchKernelGGL(k_bam_rewalk, dim3(1), dim3(64), 0, g_stream, a, k, p, to_end);
+  FQ_HIP(hipGetLastError());
+  return 0;
+}
+int launch_bam_starts(const FqBamChainArgs &a) {
+  FQ_PRE();
+  if (!a.n_seg) return 0;
+  hipLaunchKernelGGL(k_bam_starts, dim3(nblk(a.n_seg, 256)), dim3(256), 0, g_stream, a);
+  FQ_HIP(hipGetLastError());
+  return 0;
+}
+int launch_bam_keep(const FqBamPairArgs &a) {
+  FQ_PRE();
+  if (!a.n_rec) return 0;
+  hipLaunchKernelGGL(k_bam_keep, dim3(nblk(a.n_rec, 256)), dim3(256), 0, g_stream, a);
+  FQ_HIP(hipGetLastError());
+  return 0;
+}
+int launch_bam_kidx(const FqBamPairArgs &a) {
+  FQ_PRE();
+  if (!a.n_rec) return 0;
+  hipLaunchKernelGGL(k_bam_kidx, dim3(nblk(a.n_rec, 256)), dim3(256), 0, g_stream, a);
+  FQ_HIP(hipGetLastError());
+  return 0;
+}
+int launch_bam_units(const FqBamPairArgs &a) {
+  FQ_PRE();
+  if (!a.n_units) return 0;
+  hipLaunchKernelGGL(k_bam_units, dim3(nblk(a.n_units, 256)), dim3(256), 0, g_stream, a);
+  FQ_HIP(hipGetLastError());
+  return 0;
+}
+__global__ void __launch_bounds__(256) k_bam_fill_pieces(FqBamFillArgs a, int e, uint64_t n) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < n) fq_bam_fill_piece(a, e, t);
+}
+int launch_bam_fill(const FqBamFillArgs &a) {
+  FQ_PRE();
+  if (!a.n_units || a.n_sides < 1) return 0;
+  static const bool pieces = [] { const char *e = getenv("FASTQUICK_BAM_FILL"); return e && !strcmp(e, "pieces"); }();      // A/B: a thread per sixteen destination bytes (measured, DESIGN 5d: 3.1 ms against the wavefront per record's 2.7-2.8 ms per million ragged pairs)
+  if (pieces) {
+    for (int e = 0; e < a.n_sides; ++e) {
+      const uint64_t n = fq_bam_fill_pieces(a, e);
+      if (n) hipLaunchKernelGGL(k_bam_fill_pieces, dim3(nblk(n, 256)), dim3(256), 0, g_stream, a, e, n);
+    }
+    FQ_HIP(hipGetLastError());
+    return 0;
+  }
+  hipLaunchKernelGGL(k_bam_fill, dim3(nblk((uint64_t)a.n_units * (uint64_t)a.n_sides, 4)), dim3(256), 0, g_stream, a);
+  FQ_HIP(hipGetLastError());
+  return 0;
+}
+
 // dynamic-LDS limits of the kernels that ask for more than the default 64 KB: once per device (state_create)
 static int set_kernel_attributes() {
   FQ_HIP(hipFuncSetAttribute((const void *)k_sw_wave, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));

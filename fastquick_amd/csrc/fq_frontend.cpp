@@ -228,6 +228,7 @@ struct FileSide {
   std::condition_variable cv;
   bool filled[3] = {false, false, false};
   uint64_t want_text = 0;                      // text a chunk should hold (the producer's latest estimate)
+  double want_scale = 1.0;                     // BAM input: payload bytes of the one compressed side per byte of the first side's text
   bool stop = false;
   int64_t inflated_file_off = 0;               // the file offset behind the last chunk that has been inflated
   // text
@@ -252,7 +253,38 @@ struct FileSide {
 inline double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 }  // namespace
 
+namespace {
+// ---- BAM input (fq_bamin.h): the scratch of the transcoding kernels, and what a stream keeps from chunk to chunk ----
+struct BamWork {
+  DBuf<uint32_t> seg, res, starts, kept, kidx, len[2], src[2];
+  DBuf<uint64_t> base, kord, off[2], bad;
+  std::vector<uint32_t> h_seg, h_res;
+};
+struct BamChunk {                              // what the kernels found in one chunk's payload
+  uint32_t n_rec = 0, n_kept = 0, n_units = 0;
+  uint32_t chain_end = 0;                      // where the chain of whole records ends (the payload's end, or the record it cuts off)
+  uint32_t carry_from = 0;                     // ... or in front of that, the last kept record of a paired stream when it has no mate yet
+  uint32_t used_rec = 0;                       // records in front of carry_from
+  int end_flag = FQB_SEG_OK, repairs = 0, paired = 0;
+  uint64_t bad = FQB_NO_BAD, text_len[2] = {0, 0};
+};
+struct BamState {
+  bool on = false;
+  int32_t n_ref = 0, paired = 0;
+  uint64_t first_off = 0;                      // the first record's offset in the payload of the member the reader starts at
+  bool first = true;
+  BamWork W;
+  DBuf<uint8_t> d_pay[2];                      // the chunks' payloads in turn: the raw carry of one leads the next
+  int cur = 0;
+  uint64_t carry_from = 0, carry_len = 0, ord0 = 0;
+  int64_t records = 0, skipped = 0, repairs = 0;
+  double ms_starts = 0, ms_pairs = 0, ms_fill = 0;
+  double pay_total = 0, text0_total = 0;
+};
+}  // namespace
+
 struct fq_frontend {
+  BamState bam;
   int device = 0, n_files = 0, slot_mode = FQ_FASTQ_SLOTS_REUSED, batch_pairs = 262144;
   int64_t chunk_pairs = 16 * 262144;
   int max_len = 160;                           // rows the aligner sizes: a longer read ends the device's part
@@ -333,6 +365,7 @@ void reader_main(fq_frontend *fe, int e) {
     // and the kernels behind the reader have work while it reads
     static const int ramp = [] { const char *e = getenv("FASTQUICK_FE_RAMP"); const int v = e ? atoi(e) : 3; return v < 0 ? 0 : v > 5 ? 5 : v; }();      // (experiment knob: how many short chunks lead a stream)
     if (F.chunks_read < ramp) want = std::max<uint64_t>(want >> (ramp - F.chunks_read), (uint64_t)((double)fe->batch_pairs * F.text_per_record * 1.02) + (1u << 20));   // (a reference batch at least)
+    if (fe->bam.on) { std::lock_guard<std::mutex> lk(F.mu); want = (uint64_t)((double)want * F.want_scale); }
     ++F.chunks_read;
     CompChunk &C = F.chunk[k];
     C.mem.clear(); C.comp_len = 0; C.text_len = 0; C.err.clear(); C.eof = false;
@@ -423,6 +456,156 @@ void reader_main(fq_frontend *fe, int e) {
   }
 }
 
+// Members the device refused: the host's decoder, then zlib, whose verdict stands.  text: what the members' out_off count from.
+int host_inflate_refused(CompChunk &C, uint8_t *text, const std::string &path, int64_t *refused, std::string *err) {
+  std::vector<uint32_t> status(C.mem.size());
+  if (fqdev::d2h(status.data(), C.d_status.p, status.size() * 4) || fqdev::sync()) { *err = fqdev::last_error(); return FQ_ENODEV; }
+  std::unique_ptr<fqz::Inflater> fz;
+  std::vector<uint8_t> tmp, cbytes;
+  for (size_t k = 0; k < status.size(); ++k) {
+    if (status[k] == FQZ_OK) continue;
+    ++*refused;
+    const FqzMember &m = C.mem[k];
+    cbytes.resize(m.in_len + 8);
+    if (fqdev::d2h(cbytes.data(), C.d_comp.p + m.in_off, m.in_len) || fqdev::sync()) { *err = fqdev::last_error(); return FQ_ENODEV; }
+    const uint8_t *src = cbytes.data();
+    tmp.resize(m.out_len);
+    bool ok = false;
+    if (!fz) fz.reset(new fqz::Inflater);
+    if (fqz::inflate_raw(*fz, src, m.in_len, tmp.data(), m.out_len)) ok = fqz::crc32(tmp.data(), m.out_len) == m.crc;
+    else {
+      z_stream zs;
+      memset(&zs, 0, sizeof zs);
+      if (inflateInit2(&zs, -15) == Z_OK) {
+        zs.next_in = const_cast<Bytef *>(src); zs.avail_in = m.in_len; zs.next_out = tmp.data(); zs.avail_out = m.out_len;
+        const int zr = inflate(&zs, Z_FINISH);
+        ok = zr == Z_STREAM_END && zs.avail_out == 0 && (uint32_t)crc32(crc32(0L, Z_NULL, 0), tmp.data(), m.out_len) == m.crc;
+        inflateEnd(&zs);
+      }
+    }
+    if (!ok) { *err = path + ": corrupt BGZF member (inflate or CRC failed)"; return FQ_EIO; }
+    if (fqdev::h2d(text + m.out_off, tmp.data(), m.out_len) || fqdev::sync()) { *err = fqdev::last_error(); return FQ_ENODEV; }
+  }
+  return FQ_OK;
+}
+
+// ---- BAM input: records of a payload in HBM -> the two FASTQ texts (kernels: fq_bamin.h) ------------------------------------------------
+std::string bam_bad_message(uint64_t bad) {
+  const unsigned long long ord = (unsigned long long)(bad >> 3);
+  const char *what = "is refused";
+  switch ((int)(bad & 7)) {
+    case FQB_BAD_MIXED: what = "paired and single-end records are mixed in one stream"; break;
+    case FQB_BAD_LSEQ0: what = "a record without bases (l_seq == 0)"; break;
+    case FQB_BAD_FIELDS: what = "the record's fields do not fit its block_size"; break;
+    case FQB_BAD_NAME: what = "a read name byte outside 0x21..0x7e (or an empty name)"; break;
+    case FQB_BAD_MATES: what = "mates are not adjacent: collate the file by name first (the two records are not a first and a second mate)"; break;
+    case FQB_BAD_NAMES: what = "mates are not adjacent: collate the file by name first (the two records' names differ)"; break;
+  }
+  return "BAM record " + std::to_string(ord) + ": " + what;
+}
+#define FQB_TRY(x) do { if (x) { *err = fqdev::last_error(); return FQ_ENODEV; } } while (0)
+// Kernels (a) and (b) over pay[0, n): the chain of records from rec0, cut at `cuts` (the members' starts behind rec0); who is kept, who pairs with
+// whom, how long the texts are.  paired < 0: by the first kept record.  t_ms: kernel ids 4 (a) and 5 (b) of the bound state's timing.
+int bam_records(BamWork &W, const uint8_t *d_pay, uint32_t n, uint32_t rec0, const std::vector<uint32_t> &cuts, int32_t n_ref, int paired, uint64_t ord0, BamChunk *R, std::string *err) {
+  *R = BamChunk();
+  R->paired = paired < 0 ? 0 : paired;
+  R->chain_end = R->carry_from = n;
+  if (rec0 >= n) return FQ_OK;
+  // ---- (a) the members' guesses ...
+  W.h_seg.clear();
+  W.h_seg.push_back(rec0);
+  for (uint32_t c : cuts) if (c > rec0 && c < n) W.h_seg.push_back(c);
+  const uint32_t S = (uint32_t)W.h_seg.size();
+  W.h_seg.push_back(n);
+  W.h_res.assign((size_t)4 * S, 0);
+  if (!W.seg.ensure(S + 1) || !W.res.ensure((size_t)4 * S) || !W.base.ensure(S + 2)) { *err = "out of device memory (BAM records)"; return FQ_ENOMEM; }
+  FqBamChainArgs a{};
+  a.pay = d_pay; a.n = n; a.seg = W.seg.p; a.n_seg = S; a.n_ref = n_ref; a.first = W.res.p; a.last_next = W.res.p + S; a.count = W.res.p + 2 * (size_t)S; a.flag = W.res.p + 3 * (size_t)S;
+  a.base = W.base.p;
+  uint32_t *first = W.h_res.data(), *last_next = first + S, *count = first + 2 * (size_t)S, *flag = first + 3 * (size_t)S;
+  fqdev::time_begin(4);
+  FQB_TRY(fqdev::h2d(W.seg.p, W.h_seg.data(), 4 * (size_t)(S + 1)) || fqdev::launch_bam_guess(a) || fqdev::d2h(W.h_res.data(), W.res.p, 16 * (size_t)S) || fqdev::sync());
+  // ---- ... held to the chain: member k's walk stands only if it began where the chain enters k
+  uint32_t p = rec0, k = 0;
+  int relaunches = 0;
+  bool ended = false;
+  while (k < S) {
+    if (first[k] != p) {
+      ++R->repairs;
+      if (++relaunches > FQB_MAX_REPAIRS) {       // too many wrong guesses: one thread walks the rest, and every member from k on holds the chain's values
+        FQB_TRY(fqdev::launch_bam_rewalk(a, k, p, 1) || fqdev::d2h(W.h_res.data(), W.res.p, 16 * (size_t)S) || fqdev::sync());
+        relaunches = INT32_MIN;
+      } else {
+        FQB_TRY(fqdev::launch_bam_rewalk(a, k, p, 0) || fqdev::d2h(first + k, a.first + k, 4) || fqdev::d2h(last_next + k, a.last_next + k, 4) || fqdev::d2h(count + k, a.count + k, 4) ||
+                fqdev::d2h(flag + k, a.flag + k, 4) || fqdev::sync());
+      }
+      if (first[k] != p) { *err = "BAM records: the walk of a member did not start where it was told to"; return FQ_EIO; }
+    }
+    p = last_next[k];
+    if (flag[k] != FQB_SEG_OK) { R->end_flag = (int)flag[k]; ended = true; }
+    if (p >= n) ended = true;
+    ++k;
+    // members the chain jumps over (inside one record), or behind its end, hold no start -- whatever they guessed
+    while (k < S && (ended || W.h_seg[k + 1] <= p)) {
+      if (first[k] != FQB_NONE) { if (!ended) ++R->repairs; first[k] = FQB_NONE; last_next[k] = FQB_NONE; count[k] = 0; flag[k] = FQB_SEG_OK; }
+      ++k;
+    }
+  }
+  R->chain_end = R->carry_from = p;
+  uint64_t total = 0;
+  FQB_TRY(fqdev::h2d(W.res.p, W.h_res.data(), 16 * (size_t)S) || fqdev::launch_scan(a.count, W.base.p, S) || fqdev::d2h(&total, W.base.p + S, 8) || fqdev::sync());
+  if (total > 0x7fffffffull) { *err = "more than 2^31 BAM records in one chunk"; return FQ_ELIMIT; }
+  R->n_rec = R->used_rec = (uint32_t)total;
+  if (!W.starts.ensure(total + 1) || !W.kept.ensure(total + 1) || !W.kord.ensure(total + 2) || !W.kidx.ensure(total + 1) || !W.bad.ensure(2)) { *err = "out of device memory (BAM records)"; return FQ_ENOMEM; }
+  a.starts = W.starts.p;
+  FQB_TRY(fqdev::launch_bam_starts(a));
+  fqdev::time_end(4);
+  // ---- (b) kept records, pairs, lengths
+  fqdev::time_begin(5);
+  FqBamPairArgs b{};
+  b.pay = d_pay; b.starts = W.starts.p; b.n_rec = R->n_rec; b.kept = W.kept.p; b.kord = W.kord.p; b.kidx = W.kidx.p; b.ord0 = ord0; b.bad = W.bad.p;
+  uint64_t n_kept = 0;
+  FQB_TRY(fqdev::launch_bam_keep(b) || fqdev::launch_scan(W.kept.p, W.kord.p, R->n_rec) || fqdev::d2h(&n_kept, W.kord.p + R->n_rec, 8) || fqdev::sync());
+  FQB_TRY(fqdev::launch_bam_kidx(b));
+  R->n_kept = (uint32_t)n_kept;
+  auto start_of_kept = [&](uint32_t kk, uint32_t *idx, uint32_t *at) -> int {
+    return fqdev::d2h(idx, W.kidx.p + kk, 4) || fqdev::sync() || fqdev::d2h(at, W.starts.p + *idx, 4) || fqdev::sync();
+  };
+  if (paired < 0 && n_kept) {
+    uint32_t idx = 0, at = 0;
+    uint8_t fl[2] = {0, 0};
+    FQB_TRY(start_of_kept(0, &idx, &at) || fqdev::d2h(fl, d_pay + at + 18, 2) || fqdev::sync());
+    R->paired = fl[0] & 1;
+  }
+  R->n_units = R->paired ? R->n_kept / 2 : R->n_kept;
+  if (R->paired && (R->n_kept & 1)) {            // the last kept record has no mate in this payload
+    uint32_t idx = 0, at = 0;
+    FQB_TRY(start_of_kept(R->n_kept - 1, &idx, &at));
+    R->carry_from = at; R->used_rec = idx;
+  }
+  const uint32_t U = R->n_units;
+  const int sides = R->paired ? 2 : 1;
+  for (int e = 0; e < sides; ++e) if (!W.src[e].ensure(U + 1) || !W.len[e].ensure(U + 1) || !W.off[e].ensure(U + 2)) { *err = "out of device memory (BAM records)"; return FQ_ENOMEM; }
+  b.n_units = U; b.paired = R->paired;
+  for (int e = 0; e < 2; ++e) { b.src[e] = W.src[e].p; b.len[e] = W.len[e].p; }
+  const uint64_t no_bad = FQB_NO_BAD;
+  FQB_TRY(fqdev::h2d(W.bad.p, &no_bad, 8) || fqdev::launch_bam_units(b));
+  for (int e = 0; e < sides; ++e) FQB_TRY(fqdev::launch_scan(W.len[e].p, W.off[e].p, U) || fqdev::d2h(&R->text_len[e], W.off[e].p + U, 8));
+  FQB_TRY(fqdev::d2h(&R->bad, W.bad.p, 8) || fqdev::sync());
+  fqdev::time_end(5);
+  return FQ_OK;
+}
+// Kernel (c): the texts of the chunk's units at text[e] (timing id 6)
+int bam_fill(BamWork &W, const uint8_t *d_pay, const BamChunk &R, uint8_t *const text[2], std::string *err) {
+  FqBamFillArgs f{};
+  f.pay = d_pay; f.n_units = R.n_units; f.n_sides = R.paired ? 2 : 1;
+  for (int e = 0; e < f.n_sides; ++e) { f.src[e] = W.src[e].p; f.off[e] = W.off[e].p; f.text[e] = text[e]; f.total[e] = R.text_len[e]; }
+  fqdev::time_begin(6);
+  FQB_TRY(fqdev::launch_bam_fill(f));
+  fqdev::time_end(6);
+  return FQ_OK;
+}
+
 // One chunk's inflation, started one chunk ahead of the kernels that read its text (producer_main)
 struct Ahead {
   bool open = false;                // a batch slot is taken and the members of the files that still have some are being inflated
@@ -430,6 +613,70 @@ struct Ahead {
   bool has[2] = {false, false};     // the file had a compressed chunk for this one
   uint64_t H[2] = {0, 0};           // where its new text begins in d_text[slot] (a multiple of 256: the carried text goes in front of it)
 };
+
+// BAM input, one chunk: the one compressed side's members inflated into a payload buffer behind the previous chunk's raw carry (the record the
+// payload's end cut off; a last kept record without its mate), the records transcoded into both sides' d_text[slot] at their H.  Everything runs
+// on the main stream and is waited for: BAM chunks run one after the other (the text lengths are known only when kernel (b) has run).  The
+// sides' CompChunk of this turn are then made to say what the FASTQ path reads from them: text_len, eof, no member left to look at.
+int bam_chunk(fq_frontend *fe, CompChunk &C, int slot, Ahead &next, std::string *err) {
+  BamState &S = fe->bam;
+  FileSide &F0 = fe->f[0];
+  const int NF = fe->n_files;
+  if (!C.err.empty()) { *err = F0.path + ": " + C.err; return FQ_EIO; }
+  const uint64_t carry = S.carry_len, P0 = (carry + 255) & ~(uint64_t)255, n64 = P0 + C.text_len;
+  if (n64 > 0xfff00000ull) { *err = "a chunk's BAM payload exceeds 4 GiB"; return FQ_ELIMIT; }
+  const uint32_t n = (uint32_t)n64;
+  DBuf<uint8_t> &buf = S.d_pay[S.cur ^ 1];
+  if (!buf.ensure((size_t)n + 4096)) { *err = "out of device memory (BAM payload)"; return FQ_ENOMEM; }
+  if (carry) FQB_TRY(fqdev::d2d(buf.p + (P0 - carry), S.d_pay[S.cur].p + S.carry_from, (size_t)carry));
+  int64_t refused = 0;
+  if (!C.mem.empty()) {
+    for (auto &m : C.mem) m.out_off += (uint32_t)P0;
+    FqInflateArgs a{};
+    a.comp = C.d_comp.p; a.mem = C.d_mem.p; a.n_mem = (int)C.mem.size(); a.out = buf.p; a.status = C.d_status.p; a.crc = fqdev::crc_const();
+    if (!a.crc) { *err = fqdev::last_error(); return FQ_ENODEV; }
+    FQB_TRY(fqdev::h2d(C.d_mem.p, C.mem.data(), C.mem.size() * sizeof(FqzMember)));
+    fqdev::time_begin(0);
+    FQB_TRY(fqdev::launch_inflate(a));
+    fqdev::time_end(0);
+    if (const int rc = host_inflate_refused(C, buf.p, F0.path, &refused, err)) return rc;
+  }
+  const uint32_t rec0 = (uint32_t)(P0 - carry + (S.first ? S.first_off : 0));
+  S.first = false;
+  std::vector<uint32_t> cuts;
+  cuts.reserve(C.mem.size());
+  for (const auto &m : C.mem) cuts.push_back(m.out_off);
+  BamChunk R;
+  if (const int rc = bam_records(S.W, buf.p, n, rec0, cuts, S.n_ref, S.paired, S.ord0, &R, err)) return rc;
+  if (R.end_flag == FQB_SEG_CORRUPT) { *err = F0.path + ": BAM record " + std::to_string(S.ord0 + R.n_rec) + ": its block_size is not a record's"; return FQ_EIO; }
+  if (R.bad != FQB_NO_BAD) { *err = F0.path + ": " + bam_bad_message(R.bad); return FQ_EIO; }
+  if (C.eof && R.chain_end != n) { *err = F0.path + ": the stream ends inside a record (BAM record " + std::to_string(S.ord0 + R.n_rec) + ")"; return FQ_EIO; }
+  if (C.eof && R.carry_from != n) { *err = F0.path + ": " + bam_bad_message(fqb_bad(S.ord0 + R.used_rec, FQB_BAD_MATES)) + " -- the last record has no mate"; return FQ_EIO; }
+  uint8_t *text[2] = {nullptr, nullptr};
+  for (int e = 0; e < NF; ++e) {
+    FileSide &F = fe->f[e];
+    const uint64_t H = ((uint64_t)std::max<double>((double)fe->headroom_min, fe->headroom_min ? 1.5 * (double)fe->batch_pairs * F.text_per_record : 0.0) + 255) & ~(uint64_t)255;
+    next.H[e] = H; next.has[e] = true;
+    if (H + R.text_len[e] > 0xfff00000ull) { *err = "a chunk's text exceeds 4 GiB"; return FQ_ELIMIT; }
+    if (!F.d_text[slot].ensure((size_t)(H + R.text_len[e]) + 4096)) { *err = "out of device memory (text)"; return FQ_ENOMEM; }
+    text[e] = F.d_text[slot].p + H;
+  }
+  if (const int rc = bam_fill(S.W, buf.p, R, text, err)) return rc;
+  FQB_TRY(fqdev::sync());
+  // what the stream keeps
+  S.cur ^= 1; S.carry_from = R.carry_from; S.carry_len = n - R.carry_from;
+  S.ord0 += R.used_rec; S.records += R.used_rec; S.skipped += (int64_t)R.used_rec - (int64_t)R.n_units * (R.paired ? 2 : 1); S.repairs += R.repairs;
+  S.pay_total += (double)(R.carry_from - rec0); S.text0_total += (double)R.text_len[0];
+  fe->n_members += (int64_t)C.mem.size(); fe->n_refused += refused; fe->comp_bytes += (int64_t)C.comp_len; fe->text_bytes += (int64_t)(R.text_len[0] + R.text_len[1]);
+  if (S.text0_total > 0) { std::lock_guard<std::mutex> lk(F0.mu); F0.want_scale = S.pay_total / S.text0_total; }
+  const bool eof = C.eof;
+  for (int e = 0; e < NF; ++e) {
+    CompChunk &D = fe->f[e].chunk[next.comp_k];
+    D.mem.clear(); D.err.clear(); D.text_len = R.text_len[e]; D.eof = eof;
+    if (eof) fe->f[e].all_launched = true;
+  }
+  return FQ_OK;
+}
 
 // the producer: chunk after chunk until the end of the stream, a failure, or something the device does not take.
 // Two streams: the members of chunk j + 1 are inflated (aux stream) while chunk j's text is indexed, checked and keyed (main stream) -- the
@@ -486,6 +733,12 @@ void producer_main(fq_frontend *fe) {
     }
     next = Ahead();
     next.open = true; next.slot = slot; next.comp_k = comp_next;
+    if (fe->bam.on) {
+      if (Cs[0]) { std::string em; const int rc = bam_chunk(fe, *Cs[0], slot, next, &em); if (rc) { finish(rc, em, false); return -1; } }
+      ++n_started;
+      comp_next = (comp_next + 1) % 3;
+      return 1;
+    }
     FqInflateArgs ia[2] = {FqInflateArgs(), FqInflateArgs()};
     for (int e = 0; e < NF; ++e) {
       FileSide &F = fe->f[e];
@@ -577,33 +830,12 @@ void producer_main(fq_frontend *fe) {
       if (!cur.has[e]) continue;
       CompChunk &C = F.chunk[cur.comp_k];
       if (C.mem.empty()) continue;
-      std::vector<uint32_t> status(C.mem.size());
-      if (fqdev::d2h(status.data(), C.d_status.p, status.size() * 4) || fqdev::sync()) { finish(FQ_ENODEV, fqdev::last_error(), false); return; }
-      std::unique_ptr<fqz::Inflater> fz;
-      std::vector<uint8_t> tmp, cbytes;
-      for (size_t k = 0; k < status.size(); ++k) {
-        if (status[k] == FQZ_OK) continue;
-        ++TB.refused;
-        const FqzMember &m = C.mem[k];
-        cbytes.resize(m.in_len + 8);
-        if (fqdev::d2h(cbytes.data(), C.d_comp.p + m.in_off, m.in_len) || fqdev::sync()) { finish(FQ_ENODEV, fqdev::last_error(), false); return; }
-        const uint8_t *src = cbytes.data();
-        tmp.resize(m.out_len);
-        bool ok = false;
-        if (!fz) fz.reset(new fqz::Inflater);
-        if (fqz::inflate_raw(*fz, src, m.in_len, tmp.data(), m.out_len)) ok = fqz::crc32(tmp.data(), m.out_len) == m.crc;
-        else {
-          z_stream zs;
-          memset(&zs, 0, sizeof zs);
-          if (inflateInit2(&zs, -15) == Z_OK) {
-            zs.next_in = const_cast<Bytef *>(src); zs.avail_in = m.in_len; zs.next_out = tmp.data(); zs.avail_out = m.out_len;
-            const int zr = inflate(&zs, Z_FINISH);
-            ok = zr == Z_STREAM_END && zs.avail_out == 0 && (uint32_t)crc32(crc32(0L, Z_NULL, 0), tmp.data(), m.out_len) == m.crc;
-            inflateEnd(&zs);
-          }
-        }
-        if (!ok) { finish(FQ_EIO, F.path + ": corrupt BGZF member (inflate or CRC failed)", false); return; }
-        if (fqdev::h2d(F.d_text[slot].p + m.out_off, tmp.data(), m.out_len) || fqdev::sync()) { finish(FQ_ENODEV, fqdev::last_error(), false); return; }
+      {
+        std::string em;
+        int64_t n_ref = 0;
+        const int rc = host_inflate_refused(C, F.d_text[slot].p, F.path, &n_ref, &em);
+        TB.refused += n_ref;
+        if (rc) { finish(rc, em, false); return; }
       }
       TB.members += (int64_t)C.mem.size(); TB.comp_bytes += (int64_t)C.comp_len; TB.text_bytes += (int64_t)C.text_len;
     }
@@ -746,6 +978,7 @@ void producer_main(fq_frontend *fe) {
     fqdev::time_collect(t_ms, t_n, FQ_K_COUNT);
     fe->ms_inflate += t_ms[0]; fe->ms_lines += t_ms[1]; fe->ms_records += t_ms[2]; fe->ms_slots += t_ms[3]; fe->ms_tokenise += t_ms[1] + t_ms[2] + t_ms[3];
     fe->n_launch_inflate += (int64_t)t_n[0]; fe->n_chunks += 1;
+    fe->bam.ms_starts += t_ms[4]; fe->bam.ms_pairs += t_ms[5]; fe->bam.ms_fill += t_ms[6];
     fe->n_members += TB.members; fe->n_refused += TB.refused; fe->text_bytes += TB.text_bytes; fe->comp_bytes += TB.comp_bytes;
     {   // how many pairs follow this batch, by the files' sizes and the bytes a pair has taken so far (a hint: fq_align_text sizes a short first call's buffers by it)
       double left = 0;
@@ -778,6 +1011,10 @@ void producer_main(fq_frontend *fe) {
     {
       std::lock_guard<std::mutex> lk(fe->mu);
       if (n > 0) fe->ready.push_back(&TB); else fe->slot_free[slot] = true;
+      if (fall && fe->bam.on) {          // (no host reader stands behind BAM input: what would hand a FASTQ stream over is an error)
+        fe->rc = FQ_ELIMIT; fall = false; stream_end = true;
+        fe->err = fe->f[0].path + ": the text of a BAM record is not taken by the tokeniser: a read longer than the rows (" + std::to_string(fe->max_len) + " bases; --read_len), or a name it refuses";
+      }
       if (stream_end || fall) { fe->done = true; fe->fallback = fall; if (next.open) fe->slot_free[next.slot] = true; }
       fe->cv.notify_all();
     }
@@ -868,6 +1105,218 @@ extern "C" int fq_frontend_open(int device, const char *fq1, const char *fq2, in
   *out = fe.release();
   return FQ_OK;
 }
+// ---- BAM input: the host's look at the file (header, first kept record), and the open ---------------------------------------------------
+namespace {
+// the payload of a BGZF file member by member, through zlib: only for the header and the first records (fq_bam_probe)
+struct HostBgzf {
+  int fd = -1;
+  int64_t at = 0, cur_off = 0;                 // file offset of the next member; of the member `cur` came from
+  std::vector<uint8_t> cur;
+  size_t pos = 0;
+  bool not_bgzf = false, corrupt = false;
+  bool fill() {                                // the next member that holds payload; false at the end of the file or on an error
+    for (;;) {
+      uint8_t h[18 + 256];
+      const ssize_t got = pread(fd, h, sizeof h, (off_t)at);
+      if (got <= 0) return false;
+      size_t hdr = 0;
+      const size_t sz = got >= 18 ? bgzf_member(h, (size_t)got, &hdr) : 0;
+      if (sz == 0 || sz < hdr + 8) { not_bgzf = true; return false; }
+      std::vector<uint8_t> m(sz);
+      if (pread(fd, m.data(), sz, (off_t)at) != (ssize_t)sz) { corrupt = true; return false; }
+      const uint32_t isize = le32(m.data() + sz - 4);
+      cur_off = at; at += (int64_t)sz;
+      if (isize == 0) continue;
+      cur.assign(isize, 0); pos = 0;
+      z_stream zs;
+      memset(&zs, 0, sizeof zs);
+      if (inflateInit2(&zs, -15) != Z_OK) { corrupt = true; return false; }
+      zs.next_in = m.data() + hdr; zs.avail_in = (uInt)(sz - hdr - 8); zs.next_out = cur.data(); zs.avail_out = isize;
+      const int zr = inflate(&zs, Z_FINISH);
+      const bool ok = zr == Z_STREAM_END && zs.avail_out == 0;
+      inflateEnd(&zs);
+      if (!ok) { corrupt = true; return false; }
+      return true;
+    }
+  }
+  bool read(uint8_t *dst, size_t n) {          // false: the stream ends (or fails) inside these n bytes
+    while (n) {
+      if (pos == cur.size() && !fill()) return false;
+      const size_t take = std::min(n, cur.size() - pos);
+      if (dst) { memcpy(dst, cur.data() + pos, take); dst += take; }
+      pos += take; n -= take;
+    }
+    return true;
+  }
+};
+}  // namespace
+
+// The host's look at a BAM file: BGZF, magic, the header (it may span several members), where the records begin, and the first record that is
+// kept (neither secondary nor supplementary) -- its flag says paired or single-end, its l_seq sizes the rows.  Stands in for the open of the
+// reference's dormant bwa_read_bam (libbwa/bwaseqio.c:90-142).  FQ_OK, or FQ_EIO with out->error.
+extern "C" int fq_bam_probe(const char *path, fq_bam_probe_t *out) {
+  if (!path || !out) return FQ_EINVAL;
+  memset(out, 0, sizeof *out);
+  out->first_flag = -1;
+  auto fail = [&](const std::string &m) { snprintf(out->error, sizeof out->error, "%s: %s", path, m.c_str()); return FQ_EIO; };
+  HostBgzf z;
+  struct stat sb;
+  if (stat(path, &sb) != 0 || !S_ISREG(sb.st_mode)) return fail("not a regular file");
+  z.fd = open(path, O_RDONLY);
+  if (z.fd < 0) return fail("cannot be opened");
+  struct Closer { int fd; ~Closer() { close(fd); } } closer{z.fd};
+  static const uint8_t eof_block[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  uint8_t tail[28];
+  out->has_eof_block = sb.st_size >= 28 && pread(z.fd, tail, 28, (off_t)sb.st_size - 28) == 28 && memcmp(tail, eof_block, 28) == 0;
+  auto why = [&](const char *where) { return z.not_bgzf ? std::string("not a BGZF file (a BAM file is BGZF: gzip members with a BC field)") : z.corrupt ? std::string("corrupt BGZF member") : std::string("the stream ends inside ") + where; };
+  uint8_t w[8];
+  if (!z.read(w, 4)) return fail(why("the header"));
+  if (memcmp(w, "BAM\1", 4) != 0) return fail("no BAM magic at the start of the stream");
+  if (!z.read(w, 4)) return fail(why("the header"));
+  const uint32_t l_text = le32(w);
+  if ((uint64_t)l_text > (uint64_t)sb.st_size * 1100 + 65536) return fail("the header's text length is not one this file can hold");      // (DEFLATE expands by 1032 at most)
+  std::vector<uint8_t> text(l_text);
+  if (l_text && !z.read(text.data(), l_text)) return fail(why("the header"));
+  {   // @HD ... SO:value
+    const std::string t((const char *)text.data(), text.size());
+    if (t.compare(0, 3, "@HD") == 0) {
+      const size_t eol = t.find('\n'), so = t.find("\tSO:");
+      if (so != std::string::npos && (eol == std::string::npos || so < eol)) {
+        size_t e = so + 4;
+        while (e < t.size() && t[e] != '\t' && t[e] != '\n' && e - so - 4 < sizeof out->sort_order - 1) ++e;
+        memcpy(out->sort_order, t.data() + so + 4, e - so - 4);
+      }
+    }
+  }
+  if (!z.read(w, 4)) return fail(why("the header"));
+  const uint32_t n_ref = le32(w);
+  if (n_ref > 0x7fffffffu) return fail("the header's reference count is not one");
+  for (uint32_t r = 0; r < n_ref; ++r) {
+    if (!z.read(w, 4)) return fail(why("the header"));
+    const uint32_t l_name = le32(w);
+    if (l_name > (1u << 20) || !z.read(nullptr, (size_t)l_name + 4)) return fail(why("the header"));
+    out->header_bytes += 8 + (int64_t)l_name;
+  }
+  out->n_ref = (int32_t)n_ref;
+  out->header_bytes += 12 + (int64_t)l_text;
+  if (z.pos == z.cur.size()) { out->rec_member_off = z.at; out->rec_off = 0; } else { out->rec_member_off = z.cur_off; out->rec_off = (int64_t)z.pos; }
+  // the first kept record
+  for (;;) {
+    uint8_t fx[36];
+    if (!z.read(fx, 4)) break;                  // (no record, or the end: the stream's own walk says what is wrong, if anything)
+    const uint32_t bs = le32(fx);
+    if (bs < 32 || bs > FQB_MAX_BLOCK || !z.read(fx + 4, 32)) break;
+    const uint32_t flag = fx[18] | (uint32_t)fx[19] << 8;
+    if (!(flag & 0x900u)) {
+      const int32_t l = (int32_t)std::min<uint32_t>(le32(fx + 20), 0x7fffffffu);
+      if (out->first_flag >= 0) { out->first_l_seq = std::max(out->first_l_seq, l); break; }      // (the second kept record of a paired stream: the rows hold the first pair's longer read, as the FASTQ path's do)
+      out->first_flag = (int32_t)flag; out->paired = (int32_t)(flag & 1u); out->first_l_seq = l; out->first_l_name = fx[12];
+      if (!out->paired) break;
+    }
+    if (!z.read(nullptr, bs - 32)) break;
+  }
+  return FQ_OK;
+}
+
+// One BAM file -> the batches fq_frontend_open gives for the two FASTQ texts its records transcode to (include/fastquick_amd.h).
+extern "C" int fq_frontend_open_bam(int device, const char *bam, int32_t batch_pairs, int64_t chunk_pairs, int32_t slot_mode, int32_t max_read_len, fq_frontend_t **out) {
+  if (!bam || !out || batch_pairs < 1 || chunk_pairs < batch_pairs || slot_mode < 0 || slot_mode > 2 || max_read_len < 16 || max_read_len > 4096) return FQ_EINVAL;
+  *out = nullptr;
+  fq_bam_probe_t pr;
+  if (const int rc = fq_bam_probe(bam, &pr)) return rc;
+  if (!pr.has_eof_block) fprintf(stderr, "WARNING - %s: no BGZF end-of-file block at the end of the file: it may be truncated\n", bam);
+  struct StatesGuard { fqdev::State *s[3] = {nullptr, nullptr, nullptr}; bool armed = true; ~StatesGuard() { if (armed) for (fqdev::State *x : s) if (x) fqdev::state_destroy(x); } } guard;
+  std::unique_ptr<fq_frontend> fe(new fq_frontend);
+  fe->device = device; fe->batch_pairs = batch_pairs; fe->chunk_pairs = chunk_pairs / batch_pairs * batch_pairs; fe->max_len = max_read_len;
+  fe->n_files = pr.paired ? 2 : 1;
+  if (const char *ev = getenv("FASTQUICK_FE_HEADROOM")) fe->headroom_min = strtoull(ev, nullptr, 10);
+  fe->overlap = false;                           // (BAM chunks run one after the other: bam_chunk)
+  fe->slot_mode = fe->n_files == 1 ? FQ_FASTQ_SLOTS_FRESH : slot_mode;
+  fe->bam.on = true; fe->bam.n_ref = pr.n_ref; fe->bam.paired = pr.paired; fe->bam.first_off = (uint64_t)pr.rec_off;
+  const double l_name = pr.first_flag >= 0 ? (double)pr.first_l_name : 20.0, l_seq = pr.first_flag >= 0 ? (double)pr.first_l_seq : 151.0;
+  for (int e = 0; e < fe->n_files; ++e) {
+    FileSide &F = fe->f[e];
+    F.path = bam;
+    F.text_per_record = l_name + 2.0 * l_seq + 5.0;
+    F.all_launched = e > 0;                      // (one compressed side: the second text has no reader of its own)
+  }
+  {
+    FileSide &F = fe->f[0];
+    struct stat sb;
+    if (stat(bam, &sb) != 0) return FQ_EIO;
+    F.fd = open(bam, O_RDONLY);
+    if (F.fd < 0) return FQ_EIO;
+    F.file_size = (uint64_t)sb.st_size;
+    F.file_off = pr.rec_member_off;
+    F.want_scale = (double)fe->n_files * (36.0 + l_name + 1.5 * l_seq) / F.text_per_record;
+  }
+  fe->st = guard.s[0] = fqdev::state_create(device);
+  if (!fe->st || fqdev::bind(fe->st)) return FQ_ENODEV;
+  fe->f[0].st = guard.s[1] = fqdev::state_create(device);
+  if (!fe->f[0].st || fqdev::bind(fe->st)) return FQ_ENODEV;
+  const size_t n_slots = (size_t)2 * (size_t)batch_pairs;
+  for (int e = 0; e < fe->n_files; ++e) {
+    FileSide &F = fe->f[e];
+    if (!F.d_slot_base.ensure(n_slots * 96) || !F.d_slot_len.ensure(n_slots) || !F.d_slot_name.ensure(n_slots * 304) || !F.d_stat.ensure(FQT_N_STAT + 8)) return FQ_ENOMEM;
+    if (fqdev::dzero(F.d_slot_base.p, n_slots * 96) || fqdev::dzero(F.d_slot_len.p, n_slots * 2) || fqdev::dzero(F.d_slot_name.p, n_slots * 304)) return FQ_ENODEV;
+    F.want_text = (uint64_t)std::min<double>((double)kMaxText, (double)fe->chunk_pairs * F.text_per_record * 1.005 + (256 << 10));
+  }
+  if (fqdev::sync()) return FQ_ENODEV;
+  fe->f[0].read_threads = std::max(1, std::min(4, fq_host_cpus() / 2));
+  if (const char *ev = getenv("FASTQUICK_FE_READ_THREADS")) fe->f[0].read_threads = std::max(1, std::min(16, atoi(ev)));
+  fe->f[0].th = std::thread(reader_main, fe.get(), 0);
+  fe->producer = std::thread(producer_main, fe.get());
+  guard.armed = false;
+  *out = fe.release();
+  return FQ_OK;
+}
+
+// Kernels (a)-(c) on their own (tests, measurement): a payload in host memory, cut into members where the caller says.
+extern "C" int fq_bam_transcode_device(int device, const uint8_t *payload, size_t n, const int64_t *member_off, int64_t n_members, int32_t n_ref, int64_t first_record, int32_t paired,
+                                       uint8_t *text1, size_t cap1, uint8_t *text2, size_t cap2, uint32_t *starts, int64_t starts_cap, fq_bam_transcode_t *out) {
+  if (!out || (n && !payload) || n > 0xfff00000ull || first_record < 0 || (uint64_t)first_record > n || n_members < 0 || (n_members && !member_off)) return FQ_EINVAL;
+  memset(out, 0, sizeof *out);
+  DevScope scope(device);
+  if (!scope.s || fqdev::bind(scope.s)) return FQ_ENODEV;
+  int rc = FQ_OK;
+  {
+    BamWork W;
+    // (payload and texts are allocated to the byte: under the host-loop build a kernel body that reads behind the payload or writes behind a text is a sanitizer's finding)
+    DevMem d_pay, d_text[2];
+    if (!d_pay.alloc(std::max<size_t>(n, 1))) return FQ_ENOMEM;
+    if ((n && fqdev::h2d(d_pay.p, payload, n)) || fqdev::sync()) return FQ_ENODEV;
+    std::vector<uint32_t> cuts;
+    for (int64_t k = 0; k < n_members; ++k) {
+      if (member_off[k] < 0 || (uint64_t)member_off[k] > n || (k && member_off[k] < member_off[k - 1])) return FQ_EINVAL;
+      cuts.push_back((uint32_t)member_off[k]);
+    }
+    BamChunk R;
+    std::string err;
+    rc = bam_records(W, (const uint8_t *)d_pay.p, (uint32_t)n, (uint32_t)first_record, cuts, n_ref, paired, 0, &R, &err);
+    if (rc) return rc;
+    out->records = R.n_rec; out->kept = R.n_kept; out->units = R.n_units; out->used_records = R.used_rec; out->paired = R.paired; out->chain_repairs = R.repairs;
+    out->text_len[0] = (int64_t)R.text_len[0]; out->text_len[1] = (int64_t)R.text_len[1]; out->chain_end = R.chain_end; out->carry_from = R.carry_from; out->end_flag = R.end_flag;
+    out->bad_record = R.bad == FQB_NO_BAD ? -1 : (int64_t)(R.bad >> 3); out->bad_kind = R.bad == FQB_NO_BAD ? 0 : (int32_t)(R.bad & 7);
+    if (starts && R.n_rec) {
+      if ((int64_t)R.n_rec > starts_cap) return FQ_ELIMIT;
+      if (fqdev::d2h(starts, W.starts.p, 4 * (size_t)R.n_rec) || fqdev::sync()) return FQ_ENODEV;
+    }
+    if (R.bad == FQB_NO_BAD) {
+      if (R.text_len[0] > cap1 || R.text_len[1] > cap2) return FQ_ELIMIT;
+      uint8_t *text[2] = {nullptr, nullptr};
+      uint8_t *host[2] = {text1, text2};
+      for (int e = 0; e < (R.paired ? 2 : 1); ++e) { if (!d_text[e].alloc((size_t)R.text_len[e] + 3 * e + 1)) return FQ_ENOMEM; text[e] = (uint8_t *)d_text[e].p + 3 * e; }      // (the second text begins off a dword)
+      if ((rc = bam_fill(W, (const uint8_t *)d_pay.p, R, text, &err))) return rc;
+      for (int e = 0; e < (R.paired ? 2 : 1); ++e) if (R.text_len[e] && (!host[e] || fqdev::d2h(host[e], text[e], (size_t)R.text_len[e]))) return FQ_ENODEV;
+      if (fqdev::sync()) return FQ_ENODEV;
+    }
+    double ms[FQ_K_COUNT] = {0};
+    uint64_t ln[FQ_K_COUNT] = {0};
+    fqdev::time_collect(ms, ln, FQ_K_COUNT);
+    out->ms_starts = ms[4]; out->ms_pairs = ms[5]; out->ms_fill = ms[6];
+  }
+  return rc;
+}
 extern "C" void fq_frontend_close(fq_frontend_t *fe) {
   if (!fe) return;
   fqdev::State *states[3] = {fe->st, fe->f[0].st, fe->f[1].st};
@@ -902,6 +1351,7 @@ extern "C" void fq_frontend_release(fq_frontend_t *fe, fq_text_batch_t *b) {
 // released): out[e] for each file, opened with `threads` threads each.
 extern "C" int fq_frontend_handover(fq_frontend_t *fe, int threads, fq_fastq_t **out) {
   if (!fe || !out) return FQ_EINVAL;
+  if (fe->bam.on) return FQ_EINVAL;       // (BAM input: there is no host reader to hand to)
   { std::lock_guard<std::mutex> lk(fe->mu); if (!fe->done || !fe->fallback) return FQ_EINVAL; }
   if (fe->producer.joinable()) fe->producer.join();
   if (fqdev::bind(fe->st)) return FQ_ENODEV;
@@ -937,6 +1387,8 @@ extern "C" void fq_frontend_stats(const fq_frontend_t *fe, fq_frontend_stats_t *
   s->text_bytes = fe->text_bytes; s->comp_bytes = fe->comp_bytes; s->pairs = fe->pairs_done;
   s->ms_wait_reader = fe->ms_wait_reader; s->ms_wait_slot = fe->ms_wait_slot; s->ms_read = fe->f[0].ms_read + fe->f[1].ms_read; s->ms_upload = fe->f[0].ms_upload + fe->f[1].ms_upload;
   s->ms_lines = fe->ms_lines; s->ms_records = fe->ms_records; s->ms_slots = fe->ms_slots; s->inflate_launches = fe->n_launch_inflate; s->chunks = fe->n_chunks;
+  s->bam_records = fe->bam.records; s->bam_skipped = fe->bam.skipped; s->chain_repairs = fe->bam.repairs;
+  s->ms_bam_starts = fe->bam.ms_starts; s->ms_bam_pairs = fe->bam.ms_pairs; s->ms_bam_fill = fe->bam.ms_fill; s->ms_transcode = s->ms_bam_starts + s->ms_bam_pairs + s->ms_bam_fill;
 }
 // batch accessors
 extern "C" int32_t fq_text_batch_pairs(const fq_text_batch_t *b) { return b ? b->n_pairs : 0; }

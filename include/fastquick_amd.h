@@ -329,7 +329,41 @@ typedef struct {
   int64_t inflate_launches, chunks;
   double ms_wait_reader, ms_wait_slot;   /* the producer thread's waits (wall): for a chunk's compressed bytes in HBM; for a batch the caller still holds */
   double ms_read, ms_upload;             /* the reader threads' time (wall, summed over the files): pread into pinned memory; copies to HBM */
+  int64_t bam_records, bam_skipped;      /* BAM input: records taken up; of them skipped as secondary / supplementary */
+  int64_t chain_repairs;                 /* ... members whose guessed first record was not the chain's (walked again, or emptied) */
+  double ms_transcode;                   /* ... device time of the records -> text kernels: the sum of the three below */
+  double ms_bam_starts, ms_bam_pairs, ms_bam_fill;   /* record starts; keep / pair / measure; fill */
 } fq_frontend_stats_t;
+/* BAM input.  The reference refuses --bam_in (src/BwtMapper.cpp:185-187); the interface these stand in for is its dormant bwa_read_bam
+ * (libbwa/bwaseqio.c:90-142).  A BAM file X means the FASTQ texts T1 / T2 its records transcode to: records with flag 0x100 or
+ * 0x800 are skipped; the stream is paired if its first kept record has flag 0x1; kept records 2p, 2p + 1 are pair p, one with 0x40 (-> T1) and
+ * one with 0x80, names equal; a kept record is "@name\nSEQ\n+\nQUAL\n" with SEQ from the 4-bit codes, QUAL min(q + 33, 126), both turned
+ * back for flag 0x10.  fq_frontend_open_bam gives the batches fq_frontend_open gives for (T1, T2): inflating, finding the record starts,
+ * pairing and writing the text all happen on the device, chunk after chunk.
+ * fq_bam_probe: the host's look at the file -- BGZF, magic, header, the first kept record; FQ_EIO with `error` filled in.
+ * fq_frontend_open_bam: as fq_frontend_open (the probe's refusals included); fq_frontend_next returns a negative code, with
+ *   fq_frontend_last_error naming the record's ordinal (0-based, over all records of the stream), for what the contract refuses; FQ_EFALLBACK is
+ *   never returned and fq_frontend_handover is FQ_EINVAL (no host reader stands behind BAM input): a read longer than max_read_len is an error.
+ * fq_bam_transcode_device: the three kernel stages on a payload in host memory (tests, measurement): member_off[n_members] are the offsets at
+ *   which members begin (the cuts of the boundary search), first_record the offset of the first record, paired -1 (by the first kept record), 0
+ *   or 1.  starts: the record offsets.  The texts are filled when nothing is refused; FQ_ELIMIT with *out filled in when a capacity is too small. */
+typedef struct {
+  int32_t n_ref, paired, first_flag /* -1: no kept record */, first_l_seq /* of a paired stream: the longer of the first two kept records */, first_l_name, has_eof_block;
+  int64_t header_bytes, rec_member_off /* file offset of the member that holds the first record */, rec_off /* ... and the offset in its payload */;
+  char sort_order[32];                   /* @HD SO: value ("" if none) */
+  char error[256];
+} fq_bam_probe_t;
+typedef struct {
+  int64_t records, kept, units, used_records, text_len[2];
+  int64_t chain_end, carry_from;         /* where the whole records end; where what a following payload must begin with starts (an unpaired last kept record) */
+  int64_t bad_record;                    /* the first refusal: the record's ordinal (-1: none) and FQB_BAD_* kind: 1 mixed, 2 l_seq == 0, 3 fields, 4 name byte, 5 mates, 6 names */
+  int32_t bad_kind, paired, chain_repairs, end_flag;   /* end_flag: 0 the payload ends with a record, 1 inside one, 2 at a block_size that is none */
+  double ms_starts, ms_pairs, ms_fill;
+} fq_bam_transcode_t;
+int fq_bam_probe(const char *path, fq_bam_probe_t *out);
+int fq_frontend_open_bam(int device, const char *bam, int32_t batch_pairs, int64_t chunk_pairs, int32_t slot_mode, int32_t max_read_len, fq_frontend_t **out);
+int fq_bam_transcode_device(int device, const uint8_t *payload, size_t n, const int64_t *member_off, int64_t n_members, int32_t n_ref, int64_t first_record, int32_t paired,
+                            uint8_t *text1, size_t cap1, uint8_t *text2, size_t cap2, uint32_t *starts, int64_t starts_cap, fq_bam_transcode_t *out);
 int fq_frontend_open(int device, const char *fq1, const char *fq2, int32_t batch_pairs, int64_t chunk_pairs, int32_t slot_mode, int32_t max_read_len, fq_frontend_t **out);
 int64_t fq_frontend_next(fq_frontend_t *fe, fq_text_batch_t **out);
 void fq_frontend_release(fq_frontend_t *fe, fq_text_batch_t *b);
