@@ -95,7 +95,16 @@ class FrontEndStats(C.Structure):
                 ("ms_lines", C.c_double), ("ms_records", C.c_double), ("ms_slots", C.c_double), ("inflate_launches", C.c_int64), ("chunks", C.c_int64),
                 ("ms_wait_reader", C.c_double), ("ms_wait_slot", C.c_double), ("ms_read", C.c_double), ("ms_upload", C.c_double),
                 ("bam_records", C.c_int64), ("bam_skipped", C.c_int64), ("chain_repairs", C.c_int64), ("ms_transcode", C.c_double),
-                ("ms_bam_starts", C.c_double), ("ms_bam_pairs", C.c_double), ("ms_bam_fill", C.c_double)]
+                ("ms_bam_starts", C.c_double), ("ms_bam_pairs", C.c_double), ("ms_bam_fill", C.c_double),
+                ("bam_orphans", C.c_int64), ("bam_held_peak_records", C.c_int64), ("bam_held_peak_bytes", C.c_int64), ("ms_bam_collate", C.c_double)]
+
+
+class BamCollate(C.Structure):      # fq_bam_collate_t
+    _fields_ = [("records", C.c_int64), ("kept", C.c_int64), ("pairs", C.c_int64), ("orphans", C.c_int64), ("held_peak_records", C.c_int64), ("held_peak_bytes", C.c_int64),
+                ("text_len", C.c_int64 * 2), ("chain_end", C.c_int64), ("bad_record", C.c_int64),
+                ("bad_kind", C.c_int32), ("paired", C.c_int32), ("chunks", C.c_int32), ("end_flag", C.c_int32),
+                ("ms_collate", C.c_double), ("ms_keys", C.c_double), ("ms_sort", C.c_double), ("ms_match", C.c_double), ("ms_units", C.c_double), ("ms_hold", C.c_double),
+                ("error", C.c_char * 256)]
 
 
 class BamProbe(C.Structure):      # fq_bam_probe_t
@@ -119,7 +128,7 @@ EXPORTS = ["fq_default_opts", "fq_index_build", "fq_index_load", "fq_index_destr
            "fq_qc_add_last", "fq_qc_end_file", "fq_qc_write", "fq_qc_state_reset", "fq_qc_state_export", "fq_qc_merge", "fq_bam_create", "fq_bam_add_last", "fq_bam_format_last", "fq_bam_write_records", "fq_bam_close",
            "fq_fastq_open", "fq_fastq_configure", "fq_fastq_set_sampling", "fq_fastq_read", "fq_fastq_last_error", "fq_fastq_dropped_record", "fq_fastq_unequal_lengths", "fq_fastq_is_bgzf", "fq_fastq_close", "fq_inflate_raw", "fq_crc32", "fq_inflate_device", "fq_bgzf_inflate_device",
            "fq_frontend_open", "fq_frontend_next", "fq_frontend_release", "fq_frontend_handover", "fq_frontend_unequal_lengths", "fq_frontend_stats", "fq_frontend_last_error", "fq_frontend_close",
-           "fq_text_batch_pairs", "fq_text_batch_first_name", "fq_align_text", "fq_text_batch_fetch", "fq_bam_probe", "fq_frontend_open_bam", "fq_bam_transcode_device",
+           "fq_text_batch_pairs", "fq_text_batch_first_name", "fq_align_text", "fq_text_batch_fetch", "fq_bam_probe", "fq_frontend_open_bam", "fq_bam_transcode_device", "fq_frontend_open_bam_collate", "fq_bam_collate_device",
            "fq_ctx_set_emit", "fq_sam_device_last", "fq_sam_device_bytes", "fq_ctx_attach_qc", "fq_ctx_attach_bam", "fq_bgzf_deflate_device",
            "fq_bam_create_sorted", "fq_bam_sort_stats", "fq_bam_sort_stats_at_close", "fq_bam_sort_run_entries", "fq_sort_keys_device"]
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)
@@ -207,6 +216,9 @@ def load_library(path: str | None = None):
     L.fq_frontend_open.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
     L.fq_frontend_open_bam.argtypes = [C.c_int, C.c_char_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
     L.fq_bam_probe.argtypes = [C.c_char_p, C.POINTER(BamProbe)]
+    L.fq_frontend_open_bam_collate.argtypes = [C.c_int, C.c_char_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]
+    L.fq_bam_collate_device.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p,
+                                        C.c_size_t, C.POINTER(BamCollate)]
     L.fq_bam_transcode_device.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                           C.c_void_p, C.c_int64, C.POINTER(BamTranscode)]
     L.fq_frontend_next.restype = C.c_int64
@@ -825,7 +837,7 @@ def bgzf_inflate_device(blob: bytes, text_cap: int, device: int = 0, lib=None, r
 
 
 FQ_EFALLBACK = -6
-BAM_BAD_KINDS = {0: None, 1: "mixed", 2: "l_seq0", 3: "fields", 4: "name", 5: "mates", 6: "names"}      # fq_bam_transcode_t::bad_kind
+BAM_BAD_KINDS = {0: None, 1: "mixed", 2: "l_seq0", 3: "fields", 4: "name", 5: "mates", 6: "names", 7: "dup"}      # fq_bam_transcode_t::bad_kind, fq_bam_collate_t::bad_kind
 
 
 def bam_probe(path: str, lib=None) -> dict:
@@ -860,6 +872,33 @@ def bam_transcode_device(payload: bytes, member_off, n_ref: int, first_record: i
     d["text1"] = t1[:out.text_len[0]].tobytes() if out.bad_record < 0 else None
     d["text2"] = t2[:out.text_len[1]].tobytes() if out.bad_record < 0 else None
     d["starts"] = [int(x) for x in st[:out.records]]
+    return d
+
+
+def bam_collate_device(payload: bytes, member_off, n_ref: int, first_record: int = 0, members_per_chunk: int = 0, collate_mem: int = 4 << 30, paired: int = -1, device: int = 0,
+                       lib=None) -> dict:
+    """fq_bam_collate_device: the collating chunk loop on a payload -> (text1, text2, counts, orphans, held peak, first refusal, device ms by kernel);
+    members_per_chunk members a chunk (0: one chunk).  Raises FastquickError with the library's message (--collate_mem exceeded: code -5)."""
+    L = lib or load_library()
+    buf = np.frombuffer(bytes(payload) + b"\0", dtype=np.uint8)
+    n = len(payload)
+    mo = np.asarray(list(member_off), dtype=np.int64)
+    cap = 2 * n + 64
+    t1, t2 = np.zeros(cap + 64, dtype=np.uint8), np.zeros(cap + 64, dtype=np.uint8)
+    t1[cap:] = 0xa5
+    t2[cap:] = 0xa5
+    out = BamCollate()
+    rc = L.fq_bam_collate_device(device, buf.ctypes.data, n, mo.ctypes.data if mo.size else None, mo.size, members_per_chunk, n_ref, first_record, paired, collate_mem,
+                                 t1.ctypes.data, cap, t2.ctypes.data, cap, C.byref(out))
+    assert (t1[cap:] == 0xa5).all() and (t2[cap:] == 0xa5).all(), "fq_bam_collate_device wrote behind a text buffer"
+    if rc:
+        e = FastquickError("fq_bam_collate_device failed: %d (%s)" % (rc, out.error.decode(errors="replace")))
+        e.code = rc
+        raise e
+    d = {k: getattr(out, k) for k, _ in BamCollate._fields_ if k not in ("text_len", "error")}
+    d["bad_kind"] = BAM_BAD_KINDS.get(out.bad_kind, out.bad_kind)
+    d["text1"] = t1[:out.text_len[0]].tobytes() if out.bad_record < 0 else None
+    d["text2"] = t2[:out.text_len[1]].tobytes() if out.bad_record < 0 else None
     return d
 
 
@@ -968,9 +1007,13 @@ class BamFrontEnd(DeviceFrontEnd):
     transcode to.  next() never returns FQ_EFALLBACK; what the contract refuses raises with the record's ordinal in the message."""
     _open_name = "fq_frontend_open_bam"
 
-    def __init__(self, bam: str, batch_pairs: int = 262144, chunk_pairs: int = 16 * 262144, slot_mode: int = 0, max_read_len: int = 160, device: int = 0, lib=None):
+    def __init__(self, bam: str, batch_pairs: int = 262144, chunk_pairs: int = 16 * 262144, slot_mode: int = 0, max_read_len: int = 160, device: int = 0, lib=None,
+                 collate_mem: int | None = None):
         bam_probe(bam, lib=lib)      # (its message, where the file is refused)
+        self.collate_mem = collate_mem      # bytes: mates are found by name (fq_frontend_open_bam_collate); None: they are adjacent
         super().__init__(bam, None, batch_pairs, chunk_pairs, slot_mode, max_read_len, device, lib)
 
     def _open(self, device, bam, _fq2, batch_pairs, chunk_pairs, slot_mode, max_read_len):
+        if self.collate_mem is not None:
+            return self.L.fq_frontend_open_bam_collate(device, bam.encode(), batch_pairs, chunk_pairs, slot_mode, max_read_len, self.collate_mem, C.byref(self.h))
         return self.L.fq_frontend_open_bam(device, bam.encode(), batch_pairs, chunk_pairs, slot_mode, max_read_len, C.byref(self.h))

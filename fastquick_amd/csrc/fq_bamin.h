@@ -15,6 +15,11 @@
 //   (b) keep, pair      a thread per record: kept unless secondary / supplementary; a scan ranks the kept; a thread per pair (per record of a
 //                       single-end stream) checks flags and names, says which record goes to which side and how long its text is
 //   (c) fill            a wavefront per (pair, side): the four lines, a dword of destination a lane and step
+//   (b') collate        (`--collate`; in place of (b)'s pairing) mates are matched by name across the whole stream: the records that wait for their mate
+//                       are held in HBM from chunk to chunk.  Per chunk: a hash of every kept record's name; held and kept records together sorted
+//                       stably by hash (fq_sort.h); a thread per run of equal hashes walks it in ordinal order and applies the serial definition
+//                        among byte-equal names; a scan over the completing records gives the pairs their places; after the fill the
+//                       records still waiting are gathered, a wavefront each, into the other half of the held store
 #pragma once
 #include <stdint.h>
 #include <stdlib.h>
@@ -27,7 +32,7 @@
 #define FQB_MAX_REPAIRS 64                // relaunches of a member's walk in one chunk; then the serial walk
 enum { FQB_SEG_OK = 0, FQB_SEG_CUT = 1, FQB_SEG_CORRUPT = 2 };      // how a member's walk ended: at the member's end; at a record the payload's end cuts off; at a block_size that is none
 // what a record is refused for; a refusal is the pair (record ordinal, kind) as ordinal << 3 | kind, and the stream's is the smallest
-enum { FQB_BAD_MIXED = 1, FQB_BAD_LSEQ0 = 2, FQB_BAD_FIELDS = 3, FQB_BAD_NAME = 4, FQB_BAD_MATES = 5, FQB_BAD_NAMES = 6 };
+enum { FQB_BAD_MIXED = 1, FQB_BAD_LSEQ0 = 2, FQB_BAD_FIELDS = 3, FQB_BAD_NAME = 4, FQB_BAD_MATES = 5, FQB_BAD_NAMES = 6, FQB_BAD_DUP = 7 };
 #define FQB_NO_BAD 0xffffffffffffffffull
 
 // seg[0 .. n_seg]: where the members begin in the payload (seg[0]: the first record; seg[n_seg] = n); per member: first (where its walk began, or
@@ -44,7 +49,24 @@ struct FqBamPairArgs {
   uint32_t *src[2], *len[2];                                   // per unit and side: the record's offset, its text's length
   uint64_t *bad;
 };
-struct FqBamFillArgs { const uint8_t *pay; const uint32_t *src[2]; const uint64_t *off[2]; uint8_t *text[2]; uint32_t n_units; int32_t n_sides; uint64_t total[2]; };      // total[e] = off[e][n_units]
+// from[e] (collation; or null): per unit, 1 where side e's record lies in the held store -- src[e][u] is then its index there, held + hoff[index] the record
+struct FqBamFillArgs { const uint8_t *pay; const uint32_t *src[2]; const uint64_t *off[2]; uint8_t *text[2]; uint32_t n_units; int32_t n_sides; uint64_t total[2];      // total[e] = off[e][n_units]
+                       const uint8_t *held; const uint64_t *hoff; const uint8_t *from[2]; };
+// Collation.  Candidates of a chunk: the held records [0, n_held) -- older, in ordinal order -- then the chunk's kept records in chunk order.
+enum { FQC_WAIT = 0, FQC_PAIR = 1, FQC_USED = 2, FQC_BAD = 3 };      // a candidate: waits for its mate; completes a pair with mate[c]; is the earlier record of a pair; is refused
+struct FqBamCollateArgs {
+  const uint8_t *pay; const uint32_t *starts, *kidx; uint32_t n_kept; uint64_t ord0;      // the chunk's kept records
+  const uint8_t *held; const uint64_t *hoff, *hkey, *hord; uint32_t n_held;                // the held store: records, their offsets, hashes, ordinals
+  uint32_t n; uint64_t mask;                                                               // n = n_held + n_kept; the hash's bits that group
+  uint64_t *hash, *key;                                                                    // per candidate: the name's hash; hash & mask, the sort's input
+  uint32_t *st, *mate;                                                                     // per candidate: FQC_*; the candidate an FQC_PAIR completes
+  const uint64_t *skey; const uint32_t *perm;                                              // the sort's output
+  uint32_t *flag; const uint64_t *uidx;                                                    // per kept record: completes a pair; the scan: its unit
+  uint8_t *from[2]; uint32_t *src[2], *len[2];                                             // per unit and side, as FqBamFillArgs / FqBamPairArgs
+  uint64_t *bad;
+  uint32_t *surv, *rlen; const uint64_t *sidx, *soff;                                      // per candidate: still waiting; its bytes; their scans
+  uint8_t *nheld; uint64_t *noff, *nkey, *nord;                                            // the other half of the held store
+};
 
 FQ_HD uint32_t fqb_ld16(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
 FQ_HD uint32_t fqb_ld32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
@@ -175,8 +197,9 @@ FQ_HD uint8_t fq_bam_text_byte(const uint8_t *r, uint32_t nm, uint32_t l, uint32
 }
 // lane of the wavefront of (unit u, side e).  The text lies at any alignment: a lane takes an aligned dword of the destination a step, whole dwords
 // inside the record's text are stored as dwords (256 contiguous bytes a wavefront and step), the at most three bytes at either end as bytes.
+FQ_HD const uint8_t *fq_bam_fill_rec(const FqBamFillArgs &a, int e, uint32_t u) { return a.from[e] && a.from[e][u] ? a.held + a.hoff[a.src[e][u]] : a.pay + a.src[e][u]; }
 FQ_HD void fq_bam_fill_lane(const FqBamFillArgs &a, uint32_t u, int e, uint32_t lane) {
-  const uint8_t *r = a.pay + a.src[e][u];
+  const uint8_t *r = fq_bam_fill_rec(a, e, u);
   const uint32_t nm = (uint32_t)r[12] - 1u, n_cig = fqb_ld16(r + 16), l = fqb_ld32(r + 20);
   const bool rev = (fqb_ld16(r + 18) & 0x10u) != 0;
   const uint64_t len = a.off[e][u + 1] - a.off[e][u];
@@ -209,7 +232,7 @@ FQ_HD void fq_bam_fill_piece(const FqBamFillArgs &a, int e, uint64_t t) {
   while (b < hi) {
     while (u + 1 < a.n_units && a.off[e][u + 1] <= b) ++u;
     const uint64_t uend = a.off[e][u + 1] < hi ? a.off[e][u + 1] : hi;
-    const uint8_t *r = a.pay + a.src[e][u];
+    const uint8_t *r = fq_bam_fill_rec(a, e, u);
     const uint32_t nm = (uint32_t)r[12] - 1u, n_cig = fqb_ld16(r + 16), l = fqb_ld32(r + 20);
     const bool rev = (fqb_ld16(r + 18) & 0x10u) != 0;
     for (; b < uend; ++b) {
@@ -221,6 +244,91 @@ FQ_HD void fq_bam_fill_piece(const FqBamFillArgs &a, int e, uint64_t t) {
 }
 FQ_HD uint64_t fq_bam_fill_pieces(const FqBamFillArgs &a, int e) { return a.total[e] ? (a.total[e] + ((uintptr_t)a.text[e] & 15u) + 15) / 16 : 0; }
 
+// ---- (b') collation ----
+FQ_HD const uint8_t *fqc_rec(const FqBamCollateArgs &a, uint32_t c) { return c < a.n_held ? a.held + a.hoff[c] : a.pay + a.starts[a.kidx[c - a.n_held]]; }
+FQ_HD uint64_t fqc_ord(const FqBamCollateArgs &a, uint32_t c) { return c < a.n_held ? a.hord[c] : a.ord0 + a.kidx[c - a.n_held]; }
+// 64 bits of l_read_name and the name's bytes (FNV-1a, then a finaliser so that any k low bits group evenly).  The hash only groups: equality is
+// always l_read_name and a byte compare (fqc_same_name).
+FQ_HD uint64_t fqc_hash(const uint8_t *r) {
+  uint64_t h = 0xcbf29ce484222325ull;
+  const uint32_t l_name = r[12];
+  h = (h ^ l_name) * 0x100000001b3ull;
+  for (uint32_t j = 0; j < l_name; ++j) h = (h ^ r[36 + j]) * 0x100000001b3ull;
+  h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull; h ^= h >> 33;
+  return h;
+}
+FQ_HD bool fqc_same_name(const uint8_t *x, const uint8_t *y) {
+  if (x[12] != y[12]) return false;
+  for (uint32_t j = 0; j < x[12]; ++j) if (x[36 + j] != y[36 + j]) return false;
+  return true;
+}
+// candidate c: its hash and sort key; a kept record of the chunk is checked on its own (rule 3).  Returns its refusal, or FQB_NO_BAD.
+FQ_HD uint64_t fq_bam_ckey_thread(const FqBamCollateArgs &a, uint32_t c) {
+  a.mate[c] = FQB_NONE;
+  if (c < a.n_held) { a.hash[c] = a.hkey[c]; a.key[c] = a.hkey[c] & a.mask; a.st[c] = FQC_WAIT; return FQB_NO_BAD; }
+  a.flag[c - a.n_held] = 0;
+  const uint8_t *r = fqc_rec(a, c);
+  uint64_t bad = fq_bam_record_check(r, fqc_ord(a, c), 1);
+  const uint32_t side = fqb_ld16(r + 18) & 0xc0u;
+  if (bad == FQB_NO_BAD && side != 0x40u && side != 0x80u) bad = fqb_bad(fqc_ord(a, c), FQB_BAD_MATES);
+  const uint64_t h = bad == FQB_NO_BAD ? fqc_hash(r) : 0;      // (a refused record's name may not lie inside it)
+  a.hash[c] = h; a.key[c] = h & a.mask; a.st[c] = bad == FQB_NO_BAD ? FQC_WAIT : FQC_BAD;
+  return bad;
+}
+// Sorted place i: where a run of equal keys begins, its thread walks the run -- stable sort: in ordinal order -- and applies rule 4.  The nearest
+// earlier record of the same name decides: waiting with the other side bit, the two are a pair; waiting with the same side bit, this one is
+// refused; itself the later record of a pair (or no such record), this one waits.  Held records are never a pair among themselves, so only the
+// chunk's records look back.  Returns the run's first refusal, or FQB_NO_BAD.
+FQ_HD uint64_t fq_bam_cmatch_thread(const FqBamCollateArgs &a, uint32_t i) {
+  if (i && a.skey[i - 1] == a.skey[i]) return FQB_NO_BAD;
+  uint64_t bad = FQB_NO_BAD;
+  for (uint32_t t = i; t < a.n && a.skey[t] == a.skey[i]; ++t) {
+    const uint32_t c = a.perm[t];
+    if (c < a.n_held || a.st[c] == FQC_BAD) continue;
+    const uint64_t h = a.hash[c];
+    const uint8_t *r = fqc_rec(a, c);
+    for (uint32_t s = t; s > i; --s) {
+      const uint32_t w = a.perm[s - 1];
+      if (a.hash[w] != h || a.st[w] == FQC_BAD) continue;
+      const uint8_t *q = fqc_rec(a, w);
+      if (!fqc_same_name(q, r)) continue;
+      if (a.st[w] == FQC_WAIT) {
+        if (((fqb_ld16(q + 18) ^ fqb_ld16(r + 18)) & 0xc0u) == 0) { a.st[c] = FQC_BAD; bad = fqb_min64(bad, fqb_bad(fqc_ord(a, c), FQB_BAD_DUP)); }
+        else { a.st[c] = FQC_PAIR; a.mate[c] = w; a.st[w] = FQC_USED; a.flag[c - a.n_held] = 1; }
+      }
+      break;
+    }
+  }
+  return bad;
+}
+// kept record k of the chunk, where it completes a pair: the unit's two sides, the 0x40 record first (as fq_bam_unit_thread for adjacent mates)
+FQ_HD void fq_bam_cunit_thread(const FqBamCollateArgs &a, uint32_t k) {
+  if (!a.flag[k]) return;
+  const uint32_t u = (uint32_t)a.uidx[k], c = a.n_held + k, w = a.mate[c];
+  const bool c_first = (fqb_ld16(fqc_rec(a, c) + 18) & 0xc0u) == 0x40u;
+  for (int e = 0; e < 2; ++e) {
+    const uint32_t x = (e == 0) == c_first ? c : w;
+    a.from[e][u] = x < a.n_held ? 1 : 0;
+    a.src[e][u] = x < a.n_held ? x : a.starts[a.kidx[x - a.n_held]];
+    a.len[e][u] = fq_bam_text_len(fqc_rec(a, x));
+  }
+}
+// what stays: candidate c still waits -- its bytes (block_size included) -- or does not
+FQ_HD void fq_bam_cmark_thread(const FqBamCollateArgs &a, uint32_t c) {
+  const bool w = a.st[c] == FQC_WAIT;
+  a.surv[c] = w ? 1u : 0u; a.rlen[c] = w ? 4u + fqb_ld32(fqc_rec(a, c)) : 0u;
+}
+// lane of the wavefront of candidate c: a waiting record into the other half of the held store, sixty-four bytes a step (as fq_sort.h's fq_bam_gather_record_lane)
+FQ_HD void fq_bam_chold_lane(const FqBamCollateArgs &a, uint32_t c, uint32_t lane) {
+  if (!a.surv[c]) return;
+  const uint8_t *s = fqc_rec(a, c);
+  const uint64_t d0 = a.soff[c], len = a.rlen[c];
+  for (uint64_t k = lane; k < len; k += 64) a.nheld[d0 + k] = s[k];
+  if (lane == 0) { const uint64_t j = a.sidx[c]; a.noff[j] = d0; a.nkey[j] = a.hash[c]; a.nord[j] = fqc_ord(a, c); }
+}
+FQ_HD uint64_t fqc_mask(int bits) { return bits <= 0 ? 0ull : bits >= 64 ? ~0ull : (1ull << bits) - 1ull; }
+#define FQC_HASH_BITS 32      // the bits of the hash that group by default: four passes of the sort; the records of equal hashes meet in one run, and there a byte compare decides
+
 namespace fqdev {
 #if defined(__HIPCC__)
 int launch_bam_guess(const FqBamChainArgs &a);                                  // a wavefront per member: first / last_next / count / flag
@@ -230,6 +338,12 @@ int launch_bam_keep(const FqBamPairArgs &a);                                    
 int launch_bam_kidx(const FqBamPairArgs &a);
 int launch_bam_units(const FqBamPairArgs &a);                                   // a thread per pair; *a.bad lowered to the first refusal
 int launch_bam_fill(const FqBamFillArgs &a);                                    // a wavefront per (pair, side) (FASTQUICK_BAM_FILL=pieces: a thread per sixteen destination bytes, A/B)
+int bam_hash_bits();                                                            // FASTQUICK_BAM_HASH_BITS=k (0..64; tests: many names in one run), or FQC_HASH_BITS
+int launch_bam_ckeys(const FqBamCollateArgs &a);                                // a thread per candidate; *a.bad lowered
+int launch_bam_cmatch(const FqBamCollateArgs &a);                               // a thread per sorted place (per run); *a.bad lowered
+int launch_bam_cunits(const FqBamCollateArgs &a);                               // a thread per kept record
+int launch_bam_cmark(const FqBamCollateArgs &a);                                // a thread per candidate
+int launch_bam_chold(const FqBamCollateArgs &a);                                // a wavefront per candidate
 #else
 inline int launch_bam_guess(const FqBamChainArgs &a) {
   for (uint32_t k = 0; k < a.n_seg; ++k) {
@@ -250,5 +364,11 @@ inline int launch_bam_fill(const FqBamFillArgs &a) {      // (the variable is re
   for (uint32_t u = 0; u < a.n_units; ++u) for (int e = 0; e < a.n_sides; ++e) for (uint32_t lane = 0; lane < 64; ++lane) fq_bam_fill_lane(a, u, e, lane);
   return 0;
 }
+inline int bam_hash_bits() { const char *e = getenv("FASTQUICK_BAM_HASH_BITS"); const int v = e && *e ? atoi(e) : FQC_HASH_BITS; return v < 0 ? 0 : v > 64 ? 64 : v; }      // (read at every call here, as FASTQUICK_BAM_FILL)
+inline int launch_bam_ckeys(const FqBamCollateArgs &a) { for (uint32_t c = 0; c < a.n; ++c) *a.bad = fqb_min64(*a.bad, fq_bam_ckey_thread(a, c)); return 0; }
+inline int launch_bam_cmatch(const FqBamCollateArgs &a) { for (uint32_t i = 0; i < a.n; ++i) *a.bad = fqb_min64(*a.bad, fq_bam_cmatch_thread(a, i)); return 0; }
+inline int launch_bam_cunits(const FqBamCollateArgs &a) { for (uint32_t k = 0; k < a.n_kept; ++k) fq_bam_cunit_thread(a, k); return 0; }
+inline int launch_bam_cmark(const FqBamCollateArgs &a) { for (uint32_t c = 0; c < a.n; ++c) fq_bam_cmark_thread(a, c); return 0; }
+inline int launch_bam_chold(const FqBamCollateArgs &a) { for (uint32_t c = 0; c < a.n; ++c) for (uint32_t lane = 0; lane < 64; ++lane) fq_bam_chold_lane(a, c, lane); return 0; }
 #endif
 }  // namespace fqdev

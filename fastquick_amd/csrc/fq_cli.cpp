@@ -101,6 +101,9 @@ struct Args {
   bool host_consumers = false;   // --host_consumers: SAM text and StatCollector's sums on the host's threads from the result arrays (round 5's way; the default runs them in kernels, fq_emit.h)
   bool host_reader = false;   // --host_reader: the FASTQ front end on the host's threads also for BGZF files (the default inflates and tokenises them on the device)
   bool strict = false;   // --strict_reference: stop where the output could differ from the reference's bytes (today: QUAL of reads of unequal lengths)
+  bool collate = false;       // --collate: the mates of --bam_in are found by name across the file (fq_frontend_open_bam_collate: coordinate-sorted input)
+  long long collate_mem = 4ll << 30;   // --collate_mem: bytes the records waiting for their mates may take in device memory
+  bool collate_mem_given = false;
   std::string bam_in;         // --bam_in: one BAM file in place of the FASTQ files (fq_frontend_open_bam: its records are transcoded to FASTQ text on the device)
   int bam_l_seq = 0;          // ... the first kept record's length (fq_bam_probe): sizes the rows as a FASTQ file's first record does
   std::string fq_list, rg = "@RG\\tID:foo\\tSM:bar";   // runAlign's default --RG (src/FASTQuick.cpp:170)
@@ -110,7 +113,7 @@ struct Args {
 };
 
 int usage() {
-  fprintf(stderr, "Usage: FASTQuick_amd align --index_prefix P --fastq_1 R1.fq[.gz] [--fastq_2 R2.fq[.gz]] | --fq_list LIST | --bam_in X.bam  --out_prefix O [--sam_out | --sorted_bam [--sort_mem BYTES]] [--RG STR] [--cal_dup]\n"
+  fprintf(stderr, "Usage: FASTQuick_amd align --index_prefix P --fastq_1 R1.fq[.gz] [--fastq_2 R2.fq[.gz]] | --fq_list LIST | --bam_in X.bam [--collate [--collate_mem BYTES]]  --out_prefix O [--sam_out | --sorted_bam [--sort_mem BYTES]] [--RG STR] [--cal_dup]\n"
                   "                       [--q INT] [--n FLOAT|INT] [--kmer_thresh INT] [--o INT] [--e INT] [--i INT] [--d INT] [--l INT] [--k INT]\n"
                   "                       [--m INT] [--R INT] [--N] [--L] [--I] [--max_isize INT] [--max_occ INT] [--is_sw] [--n_multi INT] [--N_multi INT]\n"
                   "                       [--ap_prior FLOAT] [--force_isize] [--frac_samp FLOAT] [--t INT] [--chunk_pairs INT] [--batch_pairs INT] [--device INT | --devices LIST] [--read_len INT] [--clean_names] [--strict_reference] [--host_reader] [--host_consumers]\n"
@@ -351,7 +354,8 @@ fq_frontend_t *open_device_front_end(const Args &A, const std::string &f1, const
   if (A.host_reader || A.frac < 1.0) return nullptr;       // (--frac_samp: the reference's generator is walked record by record, on the host)
   fq_frontend_t *fe = nullptr;
   if (!A.bam_in.empty()) {
-    const int rc = fq_frontend_open_bam(device, A.bam_in.c_str(), A.o.batch_pairs, A.chunk_pairs, slot_mode, stride, &fe);
+    const int rc = A.collate ? fq_frontend_open_bam_collate(device, A.bam_in.c_str(), A.o.batch_pairs, A.chunk_pairs, slot_mode, stride, A.collate_mem, &fe)
+                             : fq_frontend_open_bam(device, A.bam_in.c_str(), A.o.batch_pairs, A.chunk_pairs, slot_mode, stride, &fe);
     mark("front end open");
     if (rc) die("--bam_in: cannot start the front end on device " + std::to_string(device) + " for " + A.bam_in + " (" + std::to_string(rc) + ")");
     return fe;
@@ -370,6 +374,10 @@ void front_end_notice(fq_frontend_t *fe) {
   if (st.bam_records || st.ms_transcode > 0)
     fprintf(stderr, "NOTICE - BAM input on the device: %lld records (%lld skipped as secondary or supplementary), %lld repairs of the record chain; records -> text %.1f ms (starts %.1f, pairs %.1f, fill %.1f)\n",
             (long long)st.bam_records, (long long)st.bam_skipped, (long long)st.chain_repairs, st.ms_transcode, st.ms_bam_starts, st.ms_bam_pairs, st.ms_bam_fill);
+  if (st.ms_bam_collate > 0 || st.bam_held_peak_records)
+    fprintf(stderr, "NOTICE - BAM input collated on the device: at most %lld records (%.1f MB) waited for their mates; collation kernels %.1f ms\n",
+            (long long)st.bam_held_peak_records, 1e-6 * (double)st.bam_held_peak_bytes, st.ms_bam_collate);
+  if (st.bam_orphans) fprintf(stderr, "WARNING - BAM input: %lld records without a mate in the file (orphans) were left out\n", (long long)st.bam_orphans);
 }
 
 
@@ -764,7 +772,7 @@ bool probe_bam_input(Args &A) {
   fq_bam_probe_t pr;
   if (fq_bam_probe(A.bam_in.c_str(), &pr)) die(std::string("--bam_in: ") + pr.error);
   A.bam_l_seq = pr.first_l_seq;
-  if (!strcmp(pr.sort_order, "coordinate")) fprintf(stderr, "NOTICE - %s says SO:coordinate: mates must be adjacent (collate the file by name first)\n", A.bam_in.c_str());
+  if (!strcmp(pr.sort_order, "coordinate") && !A.collate) fprintf(stderr, "NOTICE - %s says SO:coordinate: mates must be adjacent (collate the file by name first)\n", A.bam_in.c_str());
   return pr.paired != 0;
 }
 // --fq_list: one FASTQ pair per line, '#' lines skipped (src/BwtMapper.cpp:232-262); every pair is an independent stream
@@ -1051,6 +1059,8 @@ int main(int argc, char **argv) {
     else if (f == "--cal_dup") A.cal_dup = !A.cal_dup;        // (a bool flag on a default-1 field, like --is_sw)
     else if (f == "--frac_samp") A.frac = atof(need(""));
     else if (f == "--bam_in") A.bam_in = need("");
+    else if (f == "--collate") A.collate = true;
+    else if (f == "--collate_mem") { A.collate_mem = atoll(need("")); A.collate_mem_given = true; if (A.collate_mem < 0) die("--collate_mem must not be negative"); }
     else die("unknown option " + f);
   }
   if (A.o.fnr >= 1.0) { A.o.max_diff = (int)A.o.fnr; A.o.fnr = -1.0; }                  // src/FASTQuick.cpp:312-315
@@ -1060,6 +1070,8 @@ int main(int argc, char **argv) {
   // read filter looks at, and the re-allocation is invisible; a smaller --read_len would make it visible, and is refused.
   if (A.read_len < 96) die("--read_len must be at least 96 (the reference's is 151): below that its slot re-allocation (src/BwtMapper.cpp:536-546) would show in the read filter, and it is not modelled");
   if (A.sorted_bam && A.sam_out) die("--sorted_bam writes a BAM file: it cannot be combined with --sam_out (sorting the SAM text is not supported)");
+  if (A.collate && A.bam_in.empty()) die("--collate finds the mates of a BAM file: it needs --bam_in");
+  if (A.collate_mem_given && !A.collate) die("--collate_mem bounds what --collate holds: it needs --collate");
   if (A.out_prefix == "Empty") die("--out_prefix is required");
   if (A.index_prefix == "Empty") die("--index_prefix is required");
   R.inputs = read_inputs(A, !A.bam_in.empty() && probe_bam_input(A));

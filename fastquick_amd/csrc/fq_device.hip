@@ -1854,15 +1854,17 @@ __global__ void __launch_bounds__(256) k_bam_kidx(FqBamPairArgs a) {
   if (i < a.n_rec) fq_bam_kidx_thread(a, i);
 }
 // the first refusal: folded over the wavefront, committed by one lane and only where it lowers the value (a look first, as FQF_ATOMIC_MIN32)
-__global__ void __launch_bounds__(256) k_bam_units(FqBamPairArgs a) {
-  const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
-  uint64_t bad = u < a.n_units ? fq_bam_unit_thread(a, u) : FQB_NO_BAD;
+static __device__ __forceinline__ void bam_commit_bad(uint64_t bad, uint64_t *first) {      // (every lane of the wavefront comes here)
   for (int d = 32; d >= 1; d >>= 1) {
     const uint64_t o = (uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)bad, d, 64) | (uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(bad >> 32), d, 64) << 32;
     bad = o < bad ? o : bad;
   }
-  if ((threadIdx.x & 63u) == 0 && bad != FQB_NO_BAD && bad < __hip_atomic_load((const unsigned long long *)a.bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-    atomicMin((unsigned long long *)a.bad, (unsigned long long)bad);
+  if ((threadIdx.x & 63u) == 0 && bad != FQB_NO_BAD && bad < __hip_atomic_load((const unsigned long long *)first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+    atomicMin((unsigned long long *)first, (unsigned long long)bad);
+}
+__global__ void __launch_bounds__(256) k_bam_units(FqBamPairArgs a) {
+  const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
+  bam_commit_bad(u < a.n_units ? fq_bam_unit_thread(a, u) : FQB_NO_BAD, a.bad);
 }
 __global__ void __launch_bounds__(256) k_bam_fill(FqBamFillArgs a) {
   const uint64_t w = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -1928,6 +1930,67 @@ int launch_bam_fill(const FqBamFillArgs &a) {
     return 0;
   }
   hipLaunchKernelGGL(k_bam_fill, dim3(nblk((uint64_t)a.n_units * (uint64_t)a.n_sides, 4)), dim3(256), 0, g_stream, a);
+  FQ_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- BAM input, collation (fq_bamin.h (b')): name keys, match, units, what stays held ----
+__global__ void __launch_bounds__(256) k_bam_ckeys(FqBamCollateArgs a) {
+  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  bam_commit_bad(c < a.n ? fq_bam_ckey_thread(a, c) : FQB_NO_BAD, a.bad);
+}
+__global__ void __launch_bounds__(256) k_bam_cmatch(FqBamCollateArgs a) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  bam_commit_bad(i < a.n ? fq_bam_cmatch_thread(a, i) : FQB_NO_BAD, a.bad);
+}
+__global__ void __launch_bounds__(256) k_bam_cunits(FqBamCollateArgs a) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < a.n_kept) fq_bam_cunit_thread(a, k);
+}
+__global__ void __launch_bounds__(256) k_bam_cmark(FqBamCollateArgs a) {
+  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < a.n) fq_bam_cmark_thread(a, c);
+}
+__global__ void __launch_bounds__(256) k_bam_chold(FqBamCollateArgs a) {
+  const uint32_t c = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (c < a.n) fq_bam_chold_lane(a, c, threadIdx.x & 63u);
+}
+int bam_hash_bits() {
+  static const int bits = [] { const char *e = getenv("FASTQUICK_BAM_HASH_BITS"); const int v = e && *e ? atoi(e) : FQC_HASH_BITS; return v < 0 ? 0 : v > 64 ? 64 : v; }();
+  return bits;
+}
+int launch_bam_ckeys(const FqBamCollateArgs &a) {
+  FQ_PRE();
+  if (!a.n) return 0;
+  hipLaunchKernelGGL(k_bam_ckeys, dim3(nblk(a.n, 256)), dim3(256), 0, g_stream, a);
+  FQ_HIP(hipGetLastError());
+  return 0;
+}
+int launch_bam_cmatch(const FqBamCollateArgs &a) {
+  FQ_PRE();
+  if (!a.n) return 0;
+  hipLaunchKernelGGL(k_bam_cmatch, dim3(nblk(a.n, 256)), dim3(256), 0, g_stream, a);
+  FQ_HIP(hipGetLastError());
+  return 0;
+}
+int launch_bam_cunits(const FqBamCollateArgs &a) {
+  FQ_PRE();
+  if (!a.n_kept) return 0;
+  hipLaunchKernelGGL(k_bam_cunits, dim3(nblk(a.n_kept, 256)), dim3(256), 0, g_stream, a);
+  FQ_HIP(hipGetLastError());
+  return 0;
+}
+int launch_bam_cmark(const FqBamCollateArgs &a) {
+  FQ_PRE();
+  if (!a.n) return 0;
+  hipLaunchKernelGGL(k_bam_cmark, dim3(nblk(a.n, 256)), dim3(256), 0, g_stream, a);
+  FQ_HIP(hipGetLastError());
+  return 0;
+}
+int launch_bam_chold(const FqBamCollateArgs &a) {
+  FQ_PRE();
+  if (!a.n) return 0;
+  hipLaunchKernelGGL(k_bam_chold, dim3(nblk(a.n, 4)), dim3(256), 0, g_stream, a);
   FQ_HIP(hipGetLastError());
   return 0;
 }

@@ -268,8 +268,26 @@ struct BamChunk {                              // what the kernels found in one 
   int end_flag = FQB_SEG_OK, repairs = 0, paired = 0;
   uint64_t bad = FQB_NO_BAD, text_len[2] = {0, 0};
 };
+// --collate: the records that wait for their mates, in HBM from chunk to chunk (two halves: a chunk's survivors are gathered from one into the other),
+// with their offsets, name hashes and ordinals; and the scratch of the collation kernels
+struct BamHeld {
+  bool on = false;
+  uint64_t mem = 0;                            // collate_mem: the most a half may hold (records + 24 bytes of arrays a record)
+  DBuf<uint8_t> rec[2];
+  DBuf<uint64_t> off[2], key[2], ord[2];
+  int cur = 0;
+  uint32_t n = 0;                              // records held now
+  uint64_t bytes = 0;
+  int64_t peak_n = 0, peak_bytes = 0, orphans = 0;
+  double ms[5] = {0, 0, 0, 0, 0};              // keys, sort, match, units, held gather
+  uint32_t n_kept = 0;                         // (of the chunk under way: bam_collate_records -> bam_collate_hold)
+  DBuf<uint64_t> hash, key_in, key_out, key_tmp, hoff, uidx, sidx, soff;
+  DBuf<uint32_t> perm, perm_tmp, hist, st, mate, flag, surv, rlen;
+  DBuf<uint8_t> from[2];
+};
 struct BamState {
   bool on = false;
+  BamHeld K;
   int32_t n_ref = 0, paired = 0;
   uint64_t first_off = 0;                      // the first record's offset in the payload of the member the reader starts at
   bool first = true;
@@ -500,17 +518,14 @@ std::string bam_bad_message(uint64_t bad) {
     case FQB_BAD_NAME: what = "a read name byte outside 0x21..0x7e (or an empty name)"; break;
     case FQB_BAD_MATES: what = "mates are not adjacent: collate the file by name first (the two records are not a first and a second mate)"; break;
     case FQB_BAD_NAMES: what = "mates are not adjacent: collate the file by name first (the two records' names differ)"; break;
+    case FQB_BAD_DUP: what = "a second record of this name and side before the mate of the first"; break;
   }
   return "BAM record " + std::to_string(ord) + ": " + what;
 }
 #define FQB_TRY(x) do { if (x) { *err = fqdev::last_error(); return FQ_ENODEV; } } while (0)
-// Kernels (a) and (b) over pay[0, n): the chain of records from rec0, cut at `cuts` (the members' starts behind rec0); who is kept, who pairs with
-// whom, how long the texts are.  paired < 0: by the first kept record.  t_ms: kernel ids 4 (a) and 5 (b) of the bound state's timing.
-int bam_records(BamWork &W, const uint8_t *d_pay, uint32_t n, uint32_t rec0, const std::vector<uint32_t> &cuts, int32_t n_ref, int paired, uint64_t ord0, BamChunk *R, std::string *err) {
-  *R = BamChunk();
-  R->paired = paired < 0 ? 0 : paired;
-  R->chain_end = R->carry_from = n;
-  if (rec0 >= n) return FQ_OK;
+// Kernel (a) and the first of (b) over pay[0, n): the chain of records from rec0, cut at `cuts` (the members' starts behind rec0); who is kept, and the kept
+// records' indices -- what bam_records and its collating sibling share.  *pb: the pair kernels' arguments as far as they are known here.
+int bam_chain_kept(BamWork &W, const uint8_t *d_pay, uint32_t n, uint32_t rec0, const std::vector<uint32_t> &cuts, int32_t n_ref, uint64_t ord0, BamChunk *R, FqBamPairArgs *pb, std::string *err) {
   // ---- (a) the members' guesses ...
   W.h_seg.clear();
   W.h_seg.push_back(rec0);
@@ -562,12 +577,28 @@ int bam_records(BamWork &W, const uint8_t *d_pay, uint32_t n, uint32_t rec0, con
   fqdev::time_end(4);
   // ---- (b) kept records, pairs, lengths
   fqdev::time_begin(5);
-  FqBamPairArgs b{};
+  FqBamPairArgs &b = *pb;
+  b = FqBamPairArgs();
   b.pay = d_pay; b.starts = W.starts.p; b.n_rec = R->n_rec; b.kept = W.kept.p; b.kord = W.kord.p; b.kidx = W.kidx.p; b.ord0 = ord0; b.bad = W.bad.p;
   uint64_t n_kept = 0;
   FQB_TRY(fqdev::launch_bam_keep(b) || fqdev::launch_scan(W.kept.p, W.kord.p, R->n_rec) || fqdev::d2h(&n_kept, W.kord.p + R->n_rec, 8) || fqdev::sync());
   FQB_TRY(fqdev::launch_bam_kidx(b));
   R->n_kept = (uint32_t)n_kept;
+  fqdev::time_end(5);
+  return FQ_OK;
+}
+// Kernels (a) and (b) over pay[0, n): the chain of records from rec0, cut at `cuts` (the members' starts behind rec0); who is kept, who pairs with
+// whom, how long the texts are.  paired < 0: by the first kept record.  t_ms: kernel ids 4 (a) and 5 (b) of the bound state's timing.
+int bam_records(BamWork &W, const uint8_t *d_pay, uint32_t n, uint32_t rec0, const std::vector<uint32_t> &cuts, int32_t n_ref, int paired, uint64_t ord0, BamChunk *R, std::string *err) {
+  *R = BamChunk();
+  R->paired = paired < 0 ? 0 : paired;
+  R->chain_end = R->carry_from = n;
+  if (rec0 >= n) return FQ_OK;
+  FqBamPairArgs b{};
+  if (const int rc = bam_chain_kept(W, d_pay, n, rec0, cuts, n_ref, ord0, R, &b, err)) return rc;
+  const uint64_t n_kept = R->n_kept;
+  // ---- (b), the rest: pairs, lengths
+  fqdev::time_begin(5);
   auto start_of_kept = [&](uint32_t kk, uint32_t *idx, uint32_t *at) -> int {
     return fqdev::d2h(idx, W.kidx.p + kk, 4) || fqdev::sync() || fqdev::d2h(at, W.starts.p + *idx, 4) || fqdev::sync();
   };
@@ -596,13 +627,95 @@ int bam_records(BamWork &W, const uint8_t *d_pay, uint32_t n, uint32_t rec0, con
   return FQ_OK;
 }
 // Kernel (c): the texts of the chunk's units at text[e] (timing id 6)
-int bam_fill(BamWork &W, const uint8_t *d_pay, const BamChunk &R, uint8_t *const text[2], std::string *err) {
+int bam_fill(BamWork &W, const uint8_t *d_pay, const BamChunk &R, uint8_t *const text[2], std::string *err, const BamHeld *K = nullptr) {
   FqBamFillArgs f{};
   f.pay = d_pay; f.n_units = R.n_units; f.n_sides = R.paired ? 2 : 1;
   for (int e = 0; e < f.n_sides; ++e) { f.src[e] = W.src[e].p; f.off[e] = W.off[e].p; f.text[e] = text[e]; f.total[e] = R.text_len[e]; }
+  if (K) { f.held = K->rec[K->cur].p; f.hoff = K->off[K->cur].p; f.from[0] = K->from[0].p; f.from[1] = K->from[1].p; }      // (collation: a side's record lies in the payload or in the held store)
   fqdev::time_begin(6);
   FQB_TRY(fqdev::launch_bam_fill(f));
   fqdev::time_end(6);
+  return FQ_OK;
+}
+
+// ---- collation (--collate; fq_bamin.h (b')): in place of bam_records' pairing, mates are matched by name across the stream ----
+FqBamCollateArgs collate_args(BamWork &W, BamHeld &K, const uint8_t *d_pay, uint64_t ord0) {
+  FqBamCollateArgs c{};
+  c.pay = d_pay; c.starts = W.starts.p; c.kidx = W.kidx.p; c.n_kept = K.n_kept; c.ord0 = ord0;
+  c.held = K.rec[K.cur].p; c.hoff = K.off[K.cur].p; c.hkey = K.key[K.cur].p; c.hord = K.ord[K.cur].p; c.n_held = K.n;
+  c.n = K.n + K.n_kept; c.mask = fqc_mask(fqdev::bam_hash_bits());
+  c.hash = K.hash.p; c.key = K.key_in.p; c.st = K.st.p; c.mate = K.mate.p; c.skey = K.key_out.p; c.perm = K.perm.p; c.flag = K.flag.p; c.uidx = K.uidx.p;
+  for (int e = 0; e < 2; ++e) { c.from[e] = K.from[e].p; c.src[e] = W.src[e].p; c.len[e] = W.len[e].p; }
+  c.bad = W.bad.p; c.surv = K.surv.p; c.rlen = K.rlen.p; c.sidx = K.sidx.p; c.soff = K.soff.p;
+  c.nheld = K.rec[K.cur ^ 1].p; c.noff = K.off[K.cur ^ 1].p; c.nkey = K.key[K.cur ^ 1].p; c.nord = K.ord[K.cur ^ 1].p;
+  return c;
+}
+// The collating sibling of bam_records, for a paired stream: kernel (a) and who is kept as there; then the candidates -- the held records, then the
+// chunk's kept records -- are keyed by their names' hashes, sorted, matched run by run, and the completing records scanned into units.  Nothing but
+// the record the payload's end cuts off is carried raw: a kept record without its mate is held (bam_collate_hold, behind the fill).  Timing ids 7-10.
+int bam_collate_records(BamWork &W, BamHeld &K, const uint8_t *d_pay, uint32_t n, uint32_t rec0, const std::vector<uint32_t> &cuts, int32_t n_ref, uint64_t ord0, BamChunk *R, std::string *err) {
+  *R = BamChunk();
+  R->paired = 1;
+  R->chain_end = R->carry_from = n;
+  K.n_kept = 0;
+  if (rec0 >= n) return FQ_OK;
+  FqBamPairArgs b{};
+  if (const int rc = bam_chain_kept(W, d_pay, n, rec0, cuts, n_ref, ord0, R, &b, err)) return rc;
+  K.n_kept = R->n_kept;
+  if (!K.n_kept) return FQ_OK;                   // (no candidate of this chunk: what is held stays as it is)
+  const uint64_t N64 = (uint64_t)K.n + K.n_kept;
+  if (N64 > 0x7fffffffull) { *err = "more than 2^31 BAM records waiting for their mates"; return FQ_ELIMIT; }
+  const uint32_t N = (uint32_t)N64, tiles = fq_sort_tiles(N);
+  if (!K.hash.ensure(N) || !K.key_in.ensure(N) || !K.key_out.ensure(N) || !K.key_tmp.ensure(N) || !K.perm.ensure(N) || !K.perm_tmp.ensure(N) || !K.st.ensure(N) || !K.mate.ensure(N) ||
+      !K.hist.ensure((size_t)FQ_SORT_DIGITS * tiles + 1) || !K.hoff.ensure((size_t)FQ_SORT_DIGITS * tiles + 2) || !K.flag.ensure(K.n_kept + 1) || !K.uidx.ensure(K.n_kept + 2) ||
+      !K.surv.ensure(N + 1) || !K.rlen.ensure(N + 1) || !K.sidx.ensure(N + 2) || !K.soff.ensure(N + 2) || !W.bad.ensure(2)) { *err = "out of device memory (BAM collation)"; return FQ_ENOMEM; }
+  FqBamCollateArgs c = collate_args(W, K, d_pay, ord0);
+  const uint64_t no_bad = FQB_NO_BAD;
+  fqdev::time_begin(7);
+  FQB_TRY(fqdev::h2d(W.bad.p, &no_bad, 8) || fqdev::launch_bam_ckeys(c));
+  fqdev::time_end(7);
+  fqdev::time_begin(8);
+  const FqSortScratch sc{K.key_tmp.p, K.perm_tmp.p, K.hist.p, K.hoff.p};
+  FQB_TRY(fqdev::launch_sort_pairs(K.key_in.p, N, fqdev::bam_hash_bits(), K.key_out.p, K.perm.p, sc));
+  fqdev::time_end(8);
+  fqdev::time_begin(9);
+  FQB_TRY(fqdev::launch_bam_cmatch(c));
+  fqdev::time_end(9);
+  fqdev::time_begin(10);
+  uint64_t n_units = 0;
+  FQB_TRY(fqdev::launch_scan(K.flag.p, K.uidx.p, K.n_kept) || fqdev::d2h(&n_units, K.uidx.p + K.n_kept, 8) || fqdev::sync());
+  const uint32_t U = R->n_units = (uint32_t)n_units;
+  for (int e = 0; e < 2; ++e) if (!W.src[e].ensure(U + 1) || !W.len[e].ensure(U + 1) || !W.off[e].ensure(U + 2) || !K.from[e].ensure(U + 1)) { *err = "out of device memory (BAM collation)"; return FQ_ENOMEM; }
+  c = collate_args(W, K, d_pay, ord0);
+  FQB_TRY(fqdev::launch_bam_cunits(c));
+  for (int e = 0; e < 2; ++e) FQB_TRY(fqdev::launch_scan(W.len[e].p, W.off[e].p, U) || fqdev::d2h(&R->text_len[e], W.off[e].p + U, 8));
+  FQB_TRY(fqdev::d2h(&R->bad, W.bad.p, 8) || fqdev::sync());
+  fqdev::time_end(10);
+  return FQ_OK;
+}
+// Behind the chunk's fill: the candidates that still wait -- old held records and new ones, in ordinal order -- are gathered into the other half of the
+// held store, a wavefront a record.  FQ_ELIMIT where they would take more than collate_mem.  Timing id 11.
+int bam_collate_hold(BamWork &W, BamHeld &K, const uint8_t *d_pay, uint64_t ord0, std::string *err) {
+  if (!K.n_kept) return FQ_OK;
+  const uint32_t N = K.n + K.n_kept;
+  FqBamCollateArgs c = collate_args(W, K, d_pay, ord0);
+  uint64_t count = 0, bytes = 0;
+  fqdev::time_begin(11);
+  FQB_TRY(fqdev::launch_bam_cmark(c) || fqdev::launch_scan(K.surv.p, K.sidx.p, N) || fqdev::launch_scan(K.rlen.p, K.soff.p, N) || fqdev::d2h(&count, K.sidx.p + N, 8) || fqdev::d2h(&bytes, K.soff.p + N, 8) ||
+          fqdev::sync());
+  const uint64_t total = bytes + 24 * count;
+  if (total > K.mem) {
+    *err = "BAM record " + std::to_string(ord0) + ": behind the chunk that begins here " + std::to_string(count) + " records wait for their mates, " + std::to_string(total) +
+           " bytes: more than --collate_mem " + std::to_string(K.mem) + " (a file with many mates far apart, or many records without a mate)";
+    return FQ_ELIMIT;
+  }
+  const int o = K.cur ^ 1;
+  if (!K.rec[o].ensure((size_t)bytes + 1) || !K.off[o].ensure(count + 1) || !K.key[o].ensure(count + 1) || !K.ord[o].ensure(count + 1)) { *err = "out of device memory (BAM records waiting for their mates)"; return FQ_ENOMEM; }
+  c = collate_args(W, K, d_pay, ord0);
+  FQB_TRY(fqdev::launch_bam_chold(c) || fqdev::sync());
+  fqdev::time_end(11);
+  K.cur = o; K.n = (uint32_t)count; K.bytes = total; K.n_kept = 0;
+  K.peak_n = std::max<int64_t>(K.peak_n, (int64_t)count); K.peak_bytes = std::max<int64_t>(K.peak_bytes, (int64_t)total);
   return FQ_OK;
 }
 
@@ -647,7 +760,8 @@ int bam_chunk(fq_frontend *fe, CompChunk &C, int slot, Ahead &next, std::string 
   cuts.reserve(C.mem.size());
   for (const auto &m : C.mem) cuts.push_back(m.out_off);
   BamChunk R;
-  if (const int rc = bam_records(S.W, buf.p, n, rec0, cuts, S.n_ref, S.paired, S.ord0, &R, err)) return rc;
+  const bool collate = S.K.on && S.paired;       // (a single-end stream has no mates to find: --collate changes nothing)
+  if (const int rc = collate ? bam_collate_records(S.W, S.K, buf.p, n, rec0, cuts, S.n_ref, S.ord0, &R, err) : bam_records(S.W, buf.p, n, rec0, cuts, S.n_ref, S.paired, S.ord0, &R, err)) return rc;
   if (R.end_flag == FQB_SEG_CORRUPT) { *err = F0.path + ": BAM record " + std::to_string(S.ord0 + R.n_rec) + ": its block_size is not a record's"; return FQ_EIO; }
   if (R.bad != FQB_NO_BAD) { *err = F0.path + ": " + bam_bad_message(R.bad); return FQ_EIO; }
   if (C.eof && R.chain_end != n) { *err = F0.path + ": the stream ends inside a record (BAM record " + std::to_string(S.ord0 + R.n_rec) + ")"; return FQ_EIO; }
@@ -661,14 +775,19 @@ int bam_chunk(fq_frontend *fe, CompChunk &C, int slot, Ahead &next, std::string 
     if (!F.d_text[slot].ensure((size_t)(H + R.text_len[e]) + 4096)) { *err = "out of device memory (text)"; return FQ_ENOMEM; }
     text[e] = F.d_text[slot].p + H;
   }
-  if (const int rc = bam_fill(S.W, buf.p, R, text, err)) return rc;
+  if (const int rc = bam_fill(S.W, buf.p, R, text, err, collate ? &S.K : nullptr)) return rc;
   FQB_TRY(fqdev::sync());
+  if (collate) {
+    if (const int rc = bam_collate_hold(S.W, S.K, buf.p, S.ord0, err)) { *err = F0.path + ": " + *err; return rc; }
+    if (C.eof) S.K.orphans = S.K.n;               // what still waits at the end of the stream has no mate in it
+  }
   // what the stream keeps
   S.cur ^= 1; S.carry_from = R.carry_from; S.carry_len = n - R.carry_from;
-  S.ord0 += R.used_rec; S.records += R.used_rec; S.skipped += (int64_t)R.used_rec - (int64_t)R.n_units * (R.paired ? 2 : 1); S.repairs += R.repairs;
+  S.ord0 += R.used_rec; S.records += R.used_rec; S.skipped += collate ? (int64_t)R.n_rec - (int64_t)R.n_kept : (int64_t)R.used_rec - (int64_t)R.n_units * (R.paired ? 2 : 1); S.repairs += R.repairs;
   S.pay_total += (double)(R.carry_from - rec0); S.text0_total += (double)R.text_len[0];
   fe->n_members += (int64_t)C.mem.size(); fe->n_refused += refused; fe->comp_bytes += (int64_t)C.comp_len; fe->text_bytes += (int64_t)(R.text_len[0] + R.text_len[1]);
-  if (S.text0_total > 0) { std::lock_guard<std::mutex> lk(F0.mu); F0.want_scale = S.pay_total / S.text0_total; }
+  // (under collation a chunk's text says nothing about its payload -- it may complete no pair at all: the open's estimate of the scale stands)
+  if (S.text0_total > 0 && !collate) { std::lock_guard<std::mutex> lk(F0.mu); F0.want_scale = S.pay_total / S.text0_total; }
   const bool eof = C.eof;
   for (int e = 0; e < NF; ++e) {
     CompChunk &D = fe->f[e].chunk[next.comp_k];
@@ -979,6 +1098,7 @@ void producer_main(fq_frontend *fe) {
     fe->ms_inflate += t_ms[0]; fe->ms_lines += t_ms[1]; fe->ms_records += t_ms[2]; fe->ms_slots += t_ms[3]; fe->ms_tokenise += t_ms[1] + t_ms[2] + t_ms[3];
     fe->n_launch_inflate += (int64_t)t_n[0]; fe->n_chunks += 1;
     fe->bam.ms_starts += t_ms[4]; fe->bam.ms_pairs += t_ms[5]; fe->bam.ms_fill += t_ms[6];
+    for (int k = 0; k < 5; ++k) fe->bam.K.ms[k] += t_ms[7 + k];
     fe->n_members += TB.members; fe->n_refused += TB.refused; fe->text_bytes += TB.text_bytes; fe->comp_bytes += TB.comp_bytes;
     {   // how many pairs follow this batch, by the files' sizes and the bytes a pair has taken so far (a hint: fq_align_text sizes a short first call's buffers by it)
       double left = 0;
@@ -1219,7 +1339,8 @@ extern "C" int fq_bam_probe(const char *path, fq_bam_probe_t *out) {
 }
 
 // One BAM file -> the batches fq_frontend_open gives for the two FASTQ texts its records transcode to (include/fastquick_amd.h).
-extern "C" int fq_frontend_open_bam(int device, const char *bam, int32_t batch_pairs, int64_t chunk_pairs, int32_t slot_mode, int32_t max_read_len, fq_frontend_t **out) {
+// collate_mem < 0: mates are adjacent (fq_frontend_open_bam); otherwise they are found by name, and the records waiting for theirs take so many bytes at most.
+static int open_bam(int device, const char *bam, int32_t batch_pairs, int64_t chunk_pairs, int32_t slot_mode, int32_t max_read_len, int64_t collate_mem, fq_frontend_t **out) {
   if (!bam || !out || batch_pairs < 1 || chunk_pairs < batch_pairs || slot_mode < 0 || slot_mode > 2 || max_read_len < 16 || max_read_len > 4096) return FQ_EINVAL;
   *out = nullptr;
   fq_bam_probe_t pr;
@@ -1233,6 +1354,7 @@ extern "C" int fq_frontend_open_bam(int device, const char *bam, int32_t batch_p
   fe->overlap = false;                           // (BAM chunks run one after the other: bam_chunk)
   fe->slot_mode = fe->n_files == 1 ? FQ_FASTQ_SLOTS_FRESH : slot_mode;
   fe->bam.on = true; fe->bam.n_ref = pr.n_ref; fe->bam.paired = pr.paired; fe->bam.first_off = (uint64_t)pr.rec_off;
+  fe->bam.K.on = collate_mem >= 0; fe->bam.K.mem = collate_mem >= 0 ? (uint64_t)collate_mem : 0;
   const double l_name = pr.first_flag >= 0 ? (double)pr.first_l_name : 20.0, l_seq = pr.first_flag >= 0 ? (double)pr.first_l_seq : 151.0;
   for (int e = 0; e < fe->n_files; ++e) {
     FileSide &F = fe->f[e];
@@ -1269,6 +1391,13 @@ extern "C" int fq_frontend_open_bam(int device, const char *bam, int32_t batch_p
   guard.armed = false;
   *out = fe.release();
   return FQ_OK;
+}
+extern "C" int fq_frontend_open_bam(int device, const char *bam, int32_t batch_pairs, int64_t chunk_pairs, int32_t slot_mode, int32_t max_read_len, fq_frontend_t **out) {
+  return open_bam(device, bam, batch_pairs, chunk_pairs, slot_mode, max_read_len, -1, out);
+}
+extern "C" int fq_frontend_open_bam_collate(int device, const char *bam, int32_t batch_pairs, int64_t chunk_pairs, int32_t slot_mode, int32_t max_read_len, int64_t collate_mem_bytes, fq_frontend_t **out) {
+  if (collate_mem_bytes < 0) return FQ_EINVAL;
+  return open_bam(device, bam, batch_pairs, chunk_pairs, slot_mode, max_read_len, collate_mem_bytes, out);
 }
 
 // Kernels (a)-(c) on their own (tests, measurement): a payload in host memory, cut into members where the caller says.
@@ -1316,6 +1445,86 @@ extern "C" int fq_bam_transcode_device(int device, const uint8_t *payload, size_
     out->ms_starts = ms[4]; out->ms_pairs = ms[5]; out->ms_fill = ms[6];
   }
   return rc;
+}
+// The collating chunk loop on its own (tests, measurement): the payload is taken up in chunks of members_per_chunk members each, as the front end
+// takes up a stream -- the record a chunk's end cuts off leads the next chunk's payload, the records waiting for their mates are held in HBM --, and
+// both texts are written chunk after chunk.
+extern "C" int fq_bam_collate_device(int device, const uint8_t *payload, size_t n, const int64_t *member_off, int64_t n_members, int64_t members_per_chunk, int32_t n_ref, int64_t first_record,
+                                     int32_t paired, int64_t collate_mem_bytes, uint8_t *text1, size_t cap1, uint8_t *text2, size_t cap2, fq_bam_collate_t *out) {
+  if (!out || (n && !payload) || n > 0xfff00000ull || first_record < 0 || (uint64_t)first_record > n || n_members < 0 || (n_members && !member_off) || collate_mem_bytes < 0 || paired < -1 || paired > 1) return FQ_EINVAL;
+  memset(out, 0, sizeof *out);
+  out->bad_record = -1;
+  for (int64_t k = 0; k < n_members; ++k) if (member_off[k] < 0 || (uint64_t)member_off[k] > n || (k && member_off[k] < member_off[k - 1])) return FQ_EINVAL;
+  if (paired < 0) {      // by the first kept record (the front end knows it from fq_bam_probe)
+    paired = 0;
+    for (uint64_t p = (uint64_t)first_record; p + 36 <= n;) {
+      const uint32_t bs = le32(payload + p), flag = payload[p + 18] | (uint32_t)payload[p + 19] << 8;
+      if (bs < 32 || bs > FQB_MAX_BLOCK) break;
+      if (!(flag & 0x900u)) { paired = (int32_t)(flag & 1u); break; }
+      p += 4 + (uint64_t)bs;
+    }
+  }
+  out->paired = paired;
+  DevScope scope(device);
+  if (!scope.s || fqdev::bind(scope.s)) return FQ_ENODEV;
+  const int64_t per = members_per_chunk > 0 ? members_per_chunk : std::max<int64_t>(n_members, 1);
+  const int64_t n_chunks = std::max<int64_t>(1, (n_members + per - 1) / per);
+  BamWork W;
+  BamHeld K;
+  K.on = true; K.mem = (uint64_t)collate_mem_bytes;
+  std::vector<uint8_t> carry;                    // the record the last chunk's end cut off
+  uint64_t ord0 = 0, text_at[2] = {0, 0};
+  uint8_t *host[2] = {text1, text2};
+  const size_t cap[2] = {cap1, cap2};
+  std::string err;
+  int rc = FQ_OK;
+  auto fail = [&](int code) { snprintf(out->error, sizeof out->error, "%s", err.c_str()); return code; };
+  for (int64_t j = 0; j < n_chunks && rc == FQ_OK; ++j) {
+    const uint64_t lo = j == 0 ? 0 : (uint64_t)member_off[j * per], hi = j + 1 == n_chunks ? n : (uint64_t)member_off[(j + 1) * per];
+    const bool last = j + 1 == n_chunks;
+    if (!carry.size() && (uint64_t)first_record >= hi && !last) continue;      // (the header's chunks)
+    const uint64_t cl = carry.size(), m = cl + (hi - lo);
+    // (payload and texts are allocated to the byte, as in fq_bam_transcode_device)
+    DevMem d_pay, d_text[2];
+    if (!d_pay.alloc(std::max<size_t>((size_t)m, 1))) return FQ_ENOMEM;
+    if ((cl && fqdev::h2d(d_pay.p, carry.data(), (size_t)cl)) || (hi > lo && fqdev::h2d((uint8_t *)d_pay.p + cl, payload + lo, (size_t)(hi - lo))) || fqdev::sync()) return FQ_ENODEV;
+    const uint32_t rec0 = cl ? 0u : (uint32_t)((uint64_t)first_record > lo ? (uint64_t)first_record - lo : 0);
+    std::vector<uint32_t> cuts;
+    for (int64_t k = j * per; k < std::min<int64_t>(n_members, (j + 1) * per); ++k) if ((uint64_t)member_off[k] >= lo) cuts.push_back((uint32_t)((uint64_t)member_off[k] - lo + cl));
+    BamChunk R;
+    const bool collate = paired != 0;
+    rc = collate ? bam_collate_records(W, K, (const uint8_t *)d_pay.p, (uint32_t)m, rec0, cuts, n_ref, ord0, &R, &err) : bam_records(W, (const uint8_t *)d_pay.p, (uint32_t)m, rec0, cuts, n_ref, 0, ord0, &R, &err);
+    if (rc) return fail(rc);
+    out->chunks += 1; out->records += R.n_rec; out->kept += R.n_kept; out->pairs += R.n_units; out->end_flag = R.end_flag;
+    out->chain_end = (int64_t)(lo + R.chain_end - cl);
+    if (R.bad != FQB_NO_BAD) { out->bad_record = (int64_t)(R.bad >> 3); out->bad_kind = (int32_t)(R.bad & 7); break; }
+    if (R.end_flag == FQB_SEG_CORRUPT) break;
+    uint8_t *text[2] = {nullptr, nullptr};
+    const int sides = R.paired ? 2 : 1;
+    for (int e = 0; e < sides; ++e) {
+      if (text_at[e] + R.text_len[e] > cap[e]) { err = "a text does not fit its buffer"; return fail(FQ_ELIMIT); }
+      if (!d_text[e].alloc((size_t)R.text_len[e] + 3 * e + 1)) return FQ_ENOMEM;
+      text[e] = (uint8_t *)d_text[e].p + 3 * e;      // (the second text begins off a dword)
+    }
+    if ((rc = bam_fill(W, (const uint8_t *)d_pay.p, R, text, &err, collate ? &K : nullptr))) return fail(rc);
+    for (int e = 0; e < sides; ++e) {
+      if (R.text_len[e] && (!host[e] || fqdev::d2h(host[e] + text_at[e], text[e], (size_t)R.text_len[e]))) return FQ_ENODEV;
+      text_at[e] += R.text_len[e];
+    }
+    if (fqdev::sync()) return FQ_ENODEV;
+    if (collate && (rc = bam_collate_hold(W, K, (const uint8_t *)d_pay.p, ord0, &err))) return fail(rc);
+    ord0 += R.n_rec;
+    carry.assign((size_t)(m - R.chain_end), 0);
+    if (!carry.empty() && (fqdev::d2h(carry.data(), (const uint8_t *)d_pay.p + R.chain_end, carry.size()) || fqdev::sync())) return FQ_ENODEV;
+    double ms[FQ_K_COUNT] = {0};
+    uint64_t ln[FQ_K_COUNT] = {0};
+    fqdev::time_collect(ms, ln, FQ_K_COUNT);
+    out->ms_keys += ms[7]; out->ms_sort += ms[8]; out->ms_match += ms[9]; out->ms_units += ms[10]; out->ms_hold += ms[11];
+  }
+  out->text_len[0] = (int64_t)text_at[0]; out->text_len[1] = (int64_t)text_at[1];
+  out->orphans = K.n; out->held_peak_records = K.peak_n; out->held_peak_bytes = K.peak_bytes;
+  out->ms_collate = out->ms_keys + out->ms_sort + out->ms_match + out->ms_units + out->ms_hold;
+  return FQ_OK;
 }
 extern "C" void fq_frontend_close(fq_frontend_t *fe) {
   if (!fe) return;
@@ -1388,6 +1597,8 @@ extern "C" void fq_frontend_stats(const fq_frontend_t *fe, fq_frontend_stats_t *
   s->ms_wait_reader = fe->ms_wait_reader; s->ms_wait_slot = fe->ms_wait_slot; s->ms_read = fe->f[0].ms_read + fe->f[1].ms_read; s->ms_upload = fe->f[0].ms_upload + fe->f[1].ms_upload;
   s->ms_lines = fe->ms_lines; s->ms_records = fe->ms_records; s->ms_slots = fe->ms_slots; s->inflate_launches = fe->n_launch_inflate; s->chunks = fe->n_chunks;
   s->bam_records = fe->bam.records; s->bam_skipped = fe->bam.skipped; s->chain_repairs = fe->bam.repairs;
+  s->bam_orphans = fe->bam.K.orphans; s->bam_held_peak_records = fe->bam.K.peak_n; s->bam_held_peak_bytes = fe->bam.K.peak_bytes;
+  s->ms_bam_collate = fe->bam.K.ms[0] + fe->bam.K.ms[1] + fe->bam.K.ms[2] + fe->bam.K.ms[3] + fe->bam.K.ms[4];
   s->ms_bam_starts = fe->bam.ms_starts; s->ms_bam_pairs = fe->bam.ms_pairs; s->ms_bam_fill = fe->bam.ms_fill; s->ms_transcode = s->ms_bam_starts + s->ms_bam_pairs + s->ms_bam_fill;
 }
 // batch accessors

@@ -333,11 +333,14 @@ typedef struct {
   int64_t chain_repairs;                 /* ... members whose guessed first record was not the chain's (walked again, or emptied) */
   double ms_transcode;                   /* ... device time of the records -> text kernels: the sum of the three below */
   double ms_bam_starts, ms_bam_pairs, ms_bam_fill;   /* record starts; keep / pair / measure; fill */
+  int64_t bam_orphans;                   /* collation: kept records whose mate the stream does not hold (left out; known at the end of the stream) */
+  int64_t bam_held_peak_records, bam_held_peak_bytes;   /* ... the most records that waited for their mates behind a chunk, and their bytes (what collate_mem bounds) */
+  double ms_bam_collate;                 /* ... device time of the collation kernels: name keys, sort, match, units, held gather */
 } fq_frontend_stats_t;
 /* BAM input.  The reference refuses --bam_in (src/BwtMapper.cpp:185-187); the interface these stand in for is its dormant bwa_read_bam
  * (libbwa/bwaseqio.c:90-142).  A BAM file X means the FASTQ texts T1 / T2 its records transcode to: records with flag 0x100 or
  * 0x800 are skipped; the stream is paired if its first kept record has flag 0x1; kept records 2p, 2p + 1 are pair p, one with 0x40 (-> T1) and
- * one with 0x80, names equal; a kept record is "@name\nSEQ\n+\nQUAL\n" with SEQ from the 4-bit codes, QUAL min(q + 33, 126), both turned
+ * one with 0x80, names equal (mates elsewhere in the file: fq_frontend_open_bam_collate, below); a kept record is "@name\nSEQ\n+\nQUAL\n" with SEQ from the 4-bit codes, QUAL min(q + 33, 126), both turned
  * back for flag 0x10.  fq_frontend_open_bam gives the batches fq_frontend_open gives for (T1, T2): inflating, finding the record starts,
  * pairing and writing the text all happen on the device, chunk after chunk.
  * fq_bam_probe: the host's look at the file -- BGZF, magic, header, the first kept record; FQ_EIO with `error` filled in.
@@ -347,6 +350,30 @@ typedef struct {
  * fq_bam_transcode_device: the three kernel stages on a payload in host memory (tests, measurement): member_off[n_members] are the offsets at
  *   which members begin (the cuts of the boundary search), first_record the offset of the first record, paired -1 (by the first kept record), 0
  *   or 1.  starts: the record offsets.  The texts are filled when nothing is refused; FQ_ELIMIT with *out filled in when a capacity is too small. */
+/* Collation (`--collate`): for files whose mates are not adjacent -- coordinate-sorted ones, this library's own --sorted_bam output.
+ * fq_frontend_open_bam_collate(S) gives the batches fq_frontend_open_bam gives for the file C that holds S's header and the records this serial
+ * walk emits: records with 0x100 / 0x800 are skipped and take no part; every kept record is checked on its own (a paired record whose 0xc0 bits
+ * are neither 0x40 nor 0x80: kind 5); a map name -> record (l_read_name and the bytes) starts empty; a kept record r whose name is not in the
+ * map enters it; one that finds w there with the same side bit is refused (kind 7, "a second record of this name and side before the mate of
+ * the first", r's ordinal); with the other side bit the pair (w, r) is emitted, the 0x40 record first, and w leaves the map.  Pairs come out in
+ * the order of their later mate; what is left in the map at the end are orphans: left out and counted (fq_frontend_stats_t::bam_orphans).  A
+ * single-end stream is taken as without collation; on a file whose mates are adjacent the batches are fq_frontend_open_bam's.
+ * The waiting records are held in device memory: collate_mem_bytes bounds them (records plus 24 bytes each; the store has two halves of that
+ * size); a chunk that would leave more waiting ends the stream with FQ_ELIMIT, the message naming the ordinal at which the chunk began.
+ * fq_bam_collate_device: the collating chunk loop on a payload in host memory (tests, measurement), members_per_chunk members a chunk (<= 0:
+ *   all in one); the other arguments as fq_bam_transcode_device's.  FQ_ELIMIT with `error` filled in where collate_mem_bytes is exceeded. */
+typedef struct {
+  int64_t records, kept, pairs, orphans; /* records walked; kept; pairs written; kept records left without a mate */
+  int64_t held_peak_records, held_peak_bytes;   /* the most that waited behind a chunk */
+  int64_t text_len[2], chain_end;        /* chain_end: where the whole records end in the payload */
+  int64_t bad_record;                    /* the first refusal: ordinal (-1: none) and kind -- fq_bam_transcode_t's, and 7: a second record of a name and side before the mate of the first */
+  int32_t bad_kind, paired, chunks, end_flag;
+  double ms_collate, ms_keys, ms_sort, ms_match, ms_units, ms_hold;   /* device time of the collation kernels, and by kernel */
+  char error[256];
+} fq_bam_collate_t;
+int fq_frontend_open_bam_collate(int device, const char *bam, int32_t batch_pairs, int64_t chunk_pairs, int32_t slot_mode, int32_t max_read_len, int64_t collate_mem_bytes, fq_frontend_t **out);
+int fq_bam_collate_device(int device, const uint8_t *payload, size_t n, const int64_t *member_off, int64_t n_members, int64_t members_per_chunk, int32_t n_ref, int64_t first_record,
+                          int32_t paired, int64_t collate_mem_bytes, uint8_t *text1, size_t cap1, uint8_t *text2, size_t cap2, fq_bam_collate_t *out);
 typedef struct {
   int32_t n_ref, paired, first_flag /* -1: no kept record */, first_l_seq /* of a paired stream: the longer of the first two kept records */, first_l_name, has_eof_block;
   int64_t header_bytes, rec_member_off /* file offset of the member that holds the first record */, rec_off /* ... and the offset in its payload */;
