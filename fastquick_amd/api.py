@@ -129,7 +129,7 @@ EXPORTS = ["fq_default_opts", "fq_index_build", "fq_index_load", "fq_index_destr
            "fq_fastq_open", "fq_fastq_configure", "fq_fastq_set_sampling", "fq_fastq_read", "fq_fastq_last_error", "fq_fastq_dropped_record", "fq_fastq_unequal_lengths", "fq_fastq_is_bgzf", "fq_fastq_close", "fq_inflate_raw", "fq_crc32", "fq_inflate_device", "fq_bgzf_inflate_device",
            "fq_frontend_open", "fq_frontend_next", "fq_frontend_release", "fq_frontend_handover", "fq_frontend_unequal_lengths", "fq_frontend_stats", "fq_frontend_last_error", "fq_frontend_close",
            "fq_text_batch_pairs", "fq_text_batch_first_name", "fq_align_text", "fq_text_batch_fetch", "fq_bam_probe", "fq_frontend_open_bam", "fq_bam_transcode_device", "fq_frontend_open_bam_collate", "fq_bam_collate_device",
-           "fq_ctx_set_emit", "fq_sam_device_last", "fq_sam_device_bytes", "fq_ctx_attach_qc", "fq_ctx_attach_bam", "fq_bgzf_deflate_device",
+           "fq_ctx_set_emit", "fq_sam_device_last", "fq_sam_device_bytes", "fq_ctx_attach_qc", "fq_ctx_attach_bam", "fq_bgzf_deflate_device", "fq_bgzf_deflate_device_mode", "fq_huffman_lengths_device", "fq_bam_set_deflate", "fq_bam_deflate_stats",
            "fq_bam_create_sorted", "fq_bam_sort_stats", "fq_bam_sort_stats_at_close", "fq_bam_sort_run_entries", "fq_sort_keys_device"]
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)
 EMIT_SAM = 1
@@ -650,12 +650,17 @@ class BamSortStats(C.Structure):      # fq_bam_sort_stats_t
                 ("close_compress_sec", C.c_double), ("close_index_sec", C.c_double)]
 
 
+class BamDeflateStats(C.Structure):      # fq_bam_deflate_stats_t
+    _fields_ = [("mode", C.c_int32), ("members_fixed", C.c_int64), ("members_dynamic", C.c_int64)]
+
+
 class BamWriter:
     """The BAM consumer (SetSamRecord / SetSamFileHeader): genome-coordinate records of every batch of a stream."""
 
-    def __init__(self, index: Index, fai_path: str, bam_path: str, rg: str = "@RG\\tID:foo\\tSM:bar", sorted: bool = False, sort_mem: int = 1 << 30, **kw):
+    def __init__(self, index: Index, fai_path: str, bam_path: str, rg: str = "@RG\\tID:foo\\tSM:bar", sorted: bool = False, sort_mem: int = 1 << 30, deflate=None, **kw):
         """sorted=True: bam_path becomes the coordinate-sorted file and bam_path + ".bai" its index (fq_bam_create_sorted); the records are kept as runs,
-        up to sort_mem bytes of them in host memory, and leave at close()."""
+        up to sort_mem bytes of them in host memory, and leave at close().  deflate: "fixed" or "dynamic" -- how the device compresses the file's
+        members (fq_bam_set_deflate); None leaves the writer's default, or what FASTQUICK_BAM_DEFLATE names."""
         self.L = index.L
         self.sorted = sorted
         self._at_close = BamSortStats()
@@ -672,10 +677,28 @@ class BamWriter:
         if rc:
             raise FastquickError("fq_bam_create%s failed: %d" % ("_sorted" if sorted else "", rc))
         self.h = h
+        if deflate is not None:
+            self.set_deflate(deflate)
         if sorted:
             self.L.fq_bam_sort_stats.argtypes = [C.c_void_p, C.POINTER(BamSortStats)]
             self.L.fq_bam_sort_stats_at_close.argtypes = [C.c_void_p, C.POINTER(BamSortStats)]
             self.L.fq_bam_sort_stats_at_close(self.h, C.byref(self._at_close))
+
+    def set_deflate(self, mode):
+        """"fixed" or "dynamic" (or FQ_DEFLATE_* itself); refused once the writer has taken records"""
+        self.L.fq_bam_set_deflate.argtypes = [C.c_void_p, C.c_int]
+        rc = self.L.fq_bam_set_deflate(self.h, DEFLATE_MODES.get(mode, mode))
+        if rc:
+            raise FastquickError("fq_bam_set_deflate failed: %d" % rc)
+
+    def deflate_stats(self):
+        """(mode name, the device's members that took the fixed code, ... dynamic tables) so far; the members are counted in dynamic mode only"""
+        st = BamDeflateStats()
+        self.L.fq_bam_deflate_stats.argtypes = [C.c_void_p, C.POINTER(BamDeflateStats)]
+        rc = self.L.fq_bam_deflate_stats(self.h, C.byref(st))
+        if rc:
+            raise FastquickError("fq_bam_deflate_stats failed: %d" % rc)
+        return ("dynamic" if st.mode == 1 else "fixed"), int(st.members_fixed), int(st.members_dynamic)
 
     def write_records(self, data: bytes):
         """whole BAM records as bytes (what format_last() of another writer handed out): appended, or one more run of a sorted writer"""
@@ -794,19 +817,41 @@ def inflate_device(streams, device: int = 0, lib=None, repeats: int = 1):
     return [(int(st[k]), outs[k].raw[:streams[k][1]]) for k in range(n)], ms.value
 
 
-def bgzf_deflate_device(data: bytes, device: int = 0, lib=None):
-    """data as BGZF members written by the device's compressor (fq_deflate.h): (members, kernel_ms)"""
+DEFLATE_MODES = {"fixed": 0, "dynamic": 1}      # FQ_DEFLATE_*
+
+
+def bgzf_deflate_device(data: bytes, device: int = 0, lib=None, mode="fixed", mode_entry=False):
+    """data as BGZF members written by the device's compressor (fq_deflate.h): (members, kernel_ms).  mode "fixed": one fixed-Huffman block per
+    member; "dynamic": the block type chosen per member (never larger than the fixed encoding of the same parse).  mode_entry: "fixed" through
+    fq_bgzf_deflate_device_mode as well (the old entry otherwise)"""
     L = lib or load_library()
     n = len(data)
     cap = (n // 0xd000 + 2) * 65536
     out = np.empty(cap, dtype=np.uint8)
     src = np.frombuffer(data, dtype=np.uint8) if n else np.zeros(1, np.uint8)
     ol, ms = C.c_int64(0), C.c_double(0)
-    L.fq_bgzf_deflate_device.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
-    rc = L.fq_bgzf_deflate_device(device, src.ctypes.data, n, out.ctypes.data, cap, C.byref(ol), C.byref(ms))
+    if mode == "fixed" and not mode_entry:
+        L.fq_bgzf_deflate_device.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+        rc = L.fq_bgzf_deflate_device(device, src.ctypes.data, n, out.ctypes.data, cap, C.byref(ol), C.byref(ms))
+    else:
+        L.fq_bgzf_deflate_device_mode.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+        rc = L.fq_bgzf_deflate_device_mode(device, DEFLATE_MODES[mode], src.ctypes.data, n, out.ctypes.data, cap, C.byref(ol), C.byref(ms))
     if rc:
         raise FastquickError("fq_bgzf_deflate_device failed: %d" % rc)
     return out[:ol.value].tobytes(), ms.value
+
+
+def huffman_lengths_device(freq, limit: int, device: int = 0, lib=None):
+    """the code lengths fq_deflate.h's fqd_code_lengths makes of the frequencies, by one wavefront: a complete prefix code of at most `limit` bits
+    over the used symbols (never fewer than two codes), Huffman's lengths where those fit"""
+    L = lib or load_library()
+    f = np.ascontiguousarray(freq, dtype=np.uint32)
+    out = np.zeros(max(1, f.size), dtype=np.uint8)
+    L.fq_huffman_lengths_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    rc = L.fq_huffman_lengths_device(device, f.ctypes.data, f.size, limit, out.ctypes.data)
+    if rc:
+        raise FastquickError("fq_huffman_lengths_device failed: %d" % rc)
+    return out[:f.size]
 
 
 def sort_keys_device(keys, key_bits: int, device: int = 0, lib=None):

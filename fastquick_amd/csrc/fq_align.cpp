@@ -2239,9 +2239,10 @@ int emit_fill(Call &K) {
       // packed behind each other into a buffer sized for the worst case; their size comes back with the wait
       const uint32_t nb = (uint32_t)((total + FQD_BLOCK - 1) / FQD_BLOCK);
       CKM(c->d_zstage.ensure_roomy((size_t)nb * FQD_SLOT) && c->d_zsize.ensure((size_t)nb + 1) && c->d_zoff.ensure((size_t)nb + 2) && c->d_bamz.ensure_roomy((size_t)nb * FQD_SLOT) && c->p_ztotal.ensure(8));
-      FqDeflateArgs z{c->d_bamrec.p, total, c->d_zstage.p, c->d_zsize.p, fqdev::crc_const(), nb};
+      FqDeflateArgs z{c->d_bamrec.p, total, c->d_zstage.p, c->d_zsize.p, fqdev::crc_const(), nb, c->d_bamz.p};      // (dynamic mode keeps its tokens where the pack writes afterwards)
       if (!z.crc) { c->err = std::string("BGZF on the device: ") + fqdev::last_error(); return FQ_ENODEV; }
-      CK(fqdev::launch_deflate(z));
+      if (fq_bam_deflate_mode(c->bam) == FQ_DEFLATE_DYNAMIC) CK(fqdev::launch_deflate_dyn(z));
+      else CK(fqdev::launch_deflate(z));
       CK(fqdev::launch_scan(c->d_zsize.p, c->d_zoff.p, nb));
       FqDeflatePackArgs pk{c->d_zstage.p, c->d_zsize.p, c->d_zoff.p, c->d_bamz.p, nb};
       CK(fqdev::launch_deflate_pack(pk));

@@ -115,7 +115,7 @@ int launch_aln_index(const int32_t *work, const uint32_t *status, const uint64_t
 int launch_sam(int op, const FqSamArgs &a, int64_t n);
 int launch_bam(int op, const FqBamArgs &a, int64_t n);
 // BGZF members of a byte stream (fq_deflate.h): a wavefront per block of FQD_BLOCK bytes into its staging slot; then the members packed behind each other
-int launch_deflate(const FqDeflateArgs &a);
+int launch_deflate(const FqDeflateArgs &a);              // (launch_deflate_dyn, the block type chosen per member, stands in fq_deflate.h with its host-loop form)
 int launch_deflate_pack(const FqDeflatePackArgs &a);     // BAM records -- FQ_EOP_BAM_*, one thread per record
 // ... StatCollector's part -- operation FQ_QOP_*: a thread per pair (PAIR, IST_FILL) or per record (PILE_FILL); BASE: a wavefront per record,
 // the quality / cycle histograms of a workgroup in LDS

@@ -144,6 +144,22 @@ struct fq_bam {
   std::mutex dev_mu;
   bool dev_on = false;
   bool host_deflate = [] { const char *e = getenv("FASTQUICK_BAM_HOST_DEFLATE"); return e && *e && *e != '0'; }();   // A/B: zlib on the host's threads for device-formatted records too
+  // how the device compresses (fq_deflate.h): FQ_DEFLATE_FIXED, or FQ_DEFLATE_DYNAMIC -- the block type chosen per member; fq_bam_set_deflate wins over the variable
+  int deflate_mode = [] { const char *e = getenv("FASTQUICK_BAM_DEFLATE"); return e && !strcmp(e, "dynamic") ? FQ_DEFLATE_DYNAMIC : FQ_DEFLATE_FIXED; }();
+  bool taken = false;                                    // records have been taken: the mode stays
+  fq_bam_deflate_stats_t zst{};                          // the device's members by block type (counted in dynamic mode, from byte 18 of each as it is written)
+  fq_bam_deflate_stats_t *zst_at_close = nullptr;
+  uint8_t mem_hdr[19]; int mem_have = 0; uint64_t mem_skip = 0;
+  void count_members(const uint8_t *p, size_t n) {       // a stretch of the members' bytes, cut anywhere
+    while (n) {
+      if (mem_skip) { const size_t k = (size_t)std::min<uint64_t>(mem_skip, n); p += k; n -= k; mem_skip -= k; continue; }
+      mem_hdr[mem_have++] = *p++; --n;
+      if (mem_have == 19) {
+        ++((mem_hdr[18] >> 1 & 3) == 2 ? zst.members_dynamic : zst.members_fixed);
+        mem_skip = (uint64_t)(mem_hdr[16] | mem_hdr[17] << 8) + 1 - 19; mem_have = 0;
+      }
+    }
+  }
   std::vector<void *> d_bufs;
   const int32_t *d_rid = nullptr, *d_g0 = nullptr;
   const char *d_rg = nullptr;
@@ -253,6 +269,22 @@ bool fq_bam_sort_params(const fq_bam *b, int *n_ref, int *pos_bits, int *key_bit
   return true;
 }
 bool fq_bam_wants_members(const fq_bam *b) { return b->z.fp != nullptr && !b->host_deflate && !b->sort; }      // (a sorted writer compresses once, behind the merge)
+int fq_bam_deflate_mode(const fq_bam *b) { return b->deflate_mode; }
+extern "C" int fq_bam_set_deflate(fq_bam_t *b, int mode) {
+  if (!b || (mode != FQ_DEFLATE_FIXED && mode != FQ_DEFLATE_DYNAMIC) || b->taken) return FQ_EINVAL;
+  b->deflate_mode = mode;
+  return FQ_OK;
+}
+extern "C" int fq_bam_deflate_stats(const fq_bam_t *b, fq_bam_deflate_stats_t *out) {
+  if (!b || !out) return FQ_EINVAL;
+  *out = b->zst; out->mode = b->deflate_mode;
+  return FQ_OK;
+}
+extern "C" int fq_bam_deflate_stats_at_close(fq_bam_t *b, fq_bam_deflate_stats_t *out) {
+  if (!b) return FQ_EINVAL;
+  b->zst_at_close = out;
+  return FQ_OK;
+}
 // the formatter's part of a call's kernel arguments (on the calling context's bound state)
 int fq_bam_device_prepare(fq_bam *b, FqBamArgs *a) {
   std::lock_guard<std::mutex> lk(b->dev_mu);
@@ -466,7 +498,7 @@ static int sort_close(fq_bam_t *b) {
   std::vector<uint64_t> member_off((size_t)n_mem + 1);
   const uint32_t SLB = 256;                                   // members per slice
   const size_t SL = (size_t)SLB * FQD_BLOCK;
-  const bool on_device = !b->host_deflate;
+  const bool on_device = !b->host_deflate, dynamic = b->deflate_mode == FQ_DEFLATE_DYNAMIC;
   uint8_t *p_in = D.hm<uint8_t>(SL + 64), *p_out = D.hm<uint8_t>((size_t)SLB * FQD_SLOT);
   uint8_t *d_in = nullptr, *d_stage = nullptr, *d_out = nullptr; uint32_t *d_bs = nullptr; uint64_t *d_off = nullptr;
   if (!p_in || !p_out) { b->err = "sorted BAM: out of pinned host memory"; return FQ_ENOMEM; }
@@ -512,9 +544,9 @@ static int sort_close(fq_bam_t *b) {
     t_assemble += tc - ta;
     uint64_t zn = 0;
     if (on_device) {
-      FqDeflateArgs a{d_in, n, d_stage, d_bs, fqdev::crc_const(), nb};
+      FqDeflateArgs a{d_in, n, d_stage, d_bs, fqdev::crc_const(), nb, d_out};      // (dynamic mode keeps its tokens where the pack writes afterwards)
       FqDeflatePackArgs pk{d_stage, d_bs, d_off, d_out, nb};
-      if (fqdev::h2d(d_in, p_in, (size_t)n) || fqdev::launch_deflate(a) || fqdev::launch_scan(d_bs, d_off, nb) || fqdev::launch_deflate_pack(pk) || fqdev::d2h(&zn, d_off + nb, 8) || fqdev::sync() ||
+      if (fqdev::h2d(d_in, p_in, (size_t)n) || (dynamic ? fqdev::launch_deflate_dyn(a) : fqdev::launch_deflate(a)) || fqdev::launch_scan(d_bs, d_off, nb) || fqdev::launch_deflate_pack(pk) || fqdev::d2h(&zn, d_off + nb, 8) || fqdev::sync() ||
           zn > (uint64_t)SLB * FQD_SLOT || fqdev::d2h(p_out, d_out, (size_t)zn) || fqdev::sync()) { b->err = std::string("sorted BAM: BGZF on the device: ") + fqdev::last_error(); return FQ_ENODEV; }
     } else {
       std::vector<Bgzf::Out> outs(nb);
@@ -533,6 +565,7 @@ static int sort_close(fq_bam_t *b) {
       p += (uint64_t)fq_sort_ld16(p_out + p + 16) + 1;
     }
     if (p != zn) { b->err = "sorted BAM: the members' sizes do not add up"; return FQ_EIO; }
+    if (on_device && dynamic) b->count_members(p_out, (size_t)zn);
     b->z.write_members(p_out, (size_t)zn);
     if (!b->z.ok) return FQ_EIO;
     fpos += zn;
@@ -598,6 +631,7 @@ static int sort_close(fq_bam_t *b) {
 
 extern "C" int fq_bam_add_last(fq_bam_t *b, fq_ctx_t *c) {
   if (!b || !c || !b->z.fp) return FQ_EINVAL;
+  b->taken = true;
   if (const FqBamCallOut *D = fq_ctx_bam_out(c)) {        // the records were formatted by the call's kernels (fq_ctx_attach_bam): they only leave the device here
     if (D->owner != b || !D->ready) { b->err = "fq_bam_add_last: the context's last call formatted its records for another writer, or failed"; return FQ_EINVAL; }
     if (fq_ctx_emit_wait(c)) { b->err = "fq_bam_add_last: waiting for the call's kernels failed"; return FQ_ENODEV; }      // (z_bytes comes back with them)
@@ -616,7 +650,12 @@ extern "C" int fq_bam_add_last(fq_bam_t *b, fq_ctx_t *c) {
     int64_t n;
     if (D->z_bytes) {       // finished BGZF members (fq_deflate.h): appended behind whatever the host's layer still holds
       b->z.flush_all();
-      n = fq_ctx_bam_stream(c, [](void *user, const void *data, int64_t len) -> int { ((fq_bam *)user)->z.write_members(data, (size_t)len); return ((fq_bam *)user)->z.ok ? 0 : 1; }, b, FQ_BAM_STREAM_MEMBERS);
+      n = fq_ctx_bam_stream(c, [](void *user, const void *data, int64_t len) -> int {
+        fq_bam *w = (fq_bam *)user;
+        if (w->deflate_mode == FQ_DEFLATE_DYNAMIC) w->count_members((const uint8_t *)data, (size_t)len);
+        w->z.write_members(data, (size_t)len);
+        return w->z.ok ? 0 : 1;
+      }, b, FQ_BAM_STREAM_MEMBERS);
     } else n = fq_ctx_bam_stream(c, [](void *user, const void *data, int64_t len) -> int { ((fq_bam *)user)->z.write(data, (size_t)len); return ((fq_bam *)user)->z.ok ? 0 : 1; }, b, 0);
     if (n < 0) { b->err = "fq_bam_add_last: fetching the records from the device failed"; return (int)n; }
     return b->z.ok ? FQ_OK : FQ_EIO;
@@ -647,14 +686,16 @@ extern "C" int fq_bam_format_last(fq_bam_t *b, fq_ctx_t *c, const void **data, i
 }
 extern "C" int fq_bam_write_records(fq_bam_t *b, const void *data, int64_t len) {
   if (!b || !b->z.fp || len < 0 || (len > 0 && !data)) return FQ_EINVAL;
+  b->taken = true;
   if (b->sort) return sort_add_run(b, (const uint8_t *)data, (uint64_t)len, nullptr, 0);
   if (len) b->z.write(data, (size_t)len);
   return b->z.ok ? FQ_OK : FQ_EIO;
 }
 // (tests, tools) n bytes as BGZF members written by the device's compressor (fq_deflate.h): the members behind each other into out (capacity cap);
 // *out_len their size, *kernel_ms the compressor kernel's time.  FQ_ELIMIT when cap is too small.
-extern "C" int fq_bgzf_deflate_device(int device, const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int64_t *out_len, double *kernel_ms) {
-  if (!in || !out || !out_len || n < 0) return FQ_EINVAL;
+// mode: FQ_DEFLATE_*
+extern "C" int fq_bgzf_deflate_device_mode(int device, int mode, const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int64_t *out_len, double *kernel_ms) {
+  if (!in || !out || !out_len || n < 0 || (mode != FQ_DEFLATE_FIXED && mode != FQ_DEFLATE_DYNAMIC)) return FQ_EINVAL;
   struct DevScope { fqdev::State *s; ~DevScope() { fqdev::state_destroy(s); } } scope{fqdev::state_create(device)};
   if (!scope.s || fqdev::bind(scope.s)) return FQ_ENODEV;
   const uint32_t nb = (uint32_t)((n + FQD_BLOCK - 1) / FQD_BLOCK);
@@ -668,10 +709,10 @@ extern "C" int fq_bgzf_deflate_device(int device, const uint8_t *in, int64_t n, 
   uint64_t total = 0;
   if (!d_in || !d_stage || !d_out || !d_bs || !d_off) rc = FQ_ENOMEM;
   else {
-    FqDeflateArgs a{d_in, (uint64_t)n, d_stage, d_bs, fqdev::crc_const(), nb};
+    FqDeflateArgs a{d_in, (uint64_t)n, d_stage, d_bs, fqdev::crc_const(), nb, d_out};
     FqDeflatePackArgs pk{d_stage, d_bs, d_off, d_out, nb};
     double ms[FQ_K_COUNT] = {0}; uint64_t ln[FQ_K_COUNT] = {0};
-    if (!a.crc || fqdev::h2d(d_in, in, (size_t)n) || fqdev::launch_deflate(a) || fqdev::launch_scan(d_bs, d_off, nb) || fqdev::launch_deflate_pack(pk) ||
+    if (!a.crc || fqdev::h2d(d_in, in, (size_t)n) || (mode == FQ_DEFLATE_DYNAMIC ? fqdev::launch_deflate_dyn(a) : fqdev::launch_deflate(a)) || fqdev::launch_scan(d_bs, d_off, nb) || fqdev::launch_deflate_pack(pk) ||
         fqdev::d2h(&total, d_off + nb, 8) || fqdev::sync()) rc = FQ_ENODEV;
     else if ((int64_t)total > cap) rc = FQ_ELIMIT;
     else if (fqdev::d2h(out, d_out, (size_t)total) || fqdev::sync()) rc = FQ_ENODEV;
@@ -682,11 +723,31 @@ extern "C" int fq_bgzf_deflate_device(int device, const uint8_t *in, int64_t n, 
   *out_len = (int64_t)total;
   return rc;
 }
+extern "C" int fq_bgzf_deflate_device(int device, const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int64_t *out_len, double *kernel_ms) {
+  return fq_bgzf_deflate_device_mode(device, FQ_DEFLATE_FIXED, in, n, out, cap, out_len, kernel_ms);
+}
+// (tests) fqd_code_lengths alone, by one wavefront
+extern "C" int fq_huffman_lengths_device(int device, const uint32_t *freq, int n_sym, int limit, uint8_t *len_out) {
+  if (!freq || !len_out || n_sym < 2 || n_sym > FQD_MAX_SYMS || limit < 1 || limit > 15 || (uint32_t)n_sym > (1u << limit)) return FQ_EINVAL;
+  uint64_t sum = 0;
+  for (int s = 0; s < n_sym; ++s) sum += freq[s];
+  if (sum >> 32) return FQ_EINVAL;
+  struct DevScope { fqdev::State *s; ~DevScope() { fqdev::state_destroy(s); } } scope{fqdev::state_create(device)};
+  if (!scope.s || fqdev::bind(scope.s)) return FQ_ENODEV;
+  uint32_t *d_f = (uint32_t *)fqdev::dmalloc((size_t)n_sym * 4);
+  uint8_t *d_l = (uint8_t *)fqdev::dmalloc((size_t)n_sym);
+  int rc = FQ_OK;
+  if (!d_f || !d_l) rc = FQ_ENOMEM;
+  else if (fqdev::h2d(d_f, freq, (size_t)n_sym * 4) || fqdev::launch_code_lengths(d_f, n_sym, limit, d_l) || fqdev::d2h(len_out, d_l, (size_t)n_sym) || fqdev::sync()) rc = FQ_ENODEV;
+  fqdev::dfree(d_f); fqdev::dfree(d_l);
+  return rc;
+}
 
 extern "C" int fq_bam_close(fq_bam_t *b) {
   if (!b) return FQ_EINVAL;
   if (b->sort) {
     const int rc = sort_close(b);
+    if (b->zst_at_close) { *b->zst_at_close = b->zst; b->zst_at_close->mode = b->deflate_mode; }
     if (rc) fprintf(stderr, "fq_bam_close: %s\n", b->err.c_str());
     if (b->z.fp) { fclose(b->z.fp); b->z.fp = nullptr; }      // (after a failed close; the runs' files go with the writer)
     delete b;
@@ -694,6 +755,7 @@ extern "C" int fq_bam_close(fq_bam_t *b) {
   }
   b->z.close();
   const bool ok = b->z.ok;
+  if (b->zst_at_close) { *b->zst_at_close = b->zst; b->zst_at_close->mode = b->deflate_mode; }
   delete b;
   return ok ? FQ_OK : FQ_EIO;
 }

@@ -95,6 +95,7 @@ struct Args {
   std::string devices;   // --devices: several devices, the lines of --fq_list dealt over them
   int pack_threads = std::min(32, std::max(1, fq_host_cpus()));     // host threads of the FASTQ readers (half per file) and of the packer, from the CPUs the process may use; --t sets it
   bool clean_names = false;
+  int bam_deflate = -1;          // --bam_deflate fixed|dynamic: how the device compresses the BAM file's members (FQ_DEFLATE_*; -1: not given, the writer's default or FASTQUICK_BAM_DEFLATE)
   bool sorted_bam = false;       // --sorted_bam: <out_prefix>.sorted.bam in coordinate order and its .bai instead of <out_prefix>.bam (fq_bam_create_sorted: what the pipeline's samtools sort / index steps made of O.bam)
   long long sort_mem = 4ll << 30; // --sort_mem: bytes of records the sorted writer keeps in host memory before its runs go to files
   std::string bam_file() const { return out_prefix + (sorted_bam ? ".sorted.bam" : ".bam"); }
@@ -113,7 +114,7 @@ struct Args {
 };
 
 int usage() {
-  fprintf(stderr, "Usage: FASTQuick_amd align --index_prefix P --fastq_1 R1.fq[.gz] [--fastq_2 R2.fq[.gz]] | --fq_list LIST | --bam_in X.bam [--collate [--collate_mem BYTES]]  --out_prefix O [--sam_out | --sorted_bam [--sort_mem BYTES]] [--RG STR] [--cal_dup]\n"
+  fprintf(stderr, "Usage: FASTQuick_amd align --index_prefix P --fastq_1 R1.fq[.gz] [--fastq_2 R2.fq[.gz]] | --fq_list LIST | --bam_in X.bam [--collate [--collate_mem BYTES]]  --out_prefix O [--sam_out | --sorted_bam [--sort_mem BYTES]] [--bam_deflate fixed|dynamic] [--RG STR] [--cal_dup]\n"
                   "                       [--q INT] [--n FLOAT|INT] [--kmer_thresh INT] [--o INT] [--e INT] [--i INT] [--d INT] [--l INT] [--k INT]\n"
                   "                       [--m INT] [--R INT] [--N] [--L] [--I] [--max_isize INT] [--max_occ INT] [--is_sw] [--n_multi INT] [--N_multi INT]\n"
                   "                       [--ap_prior FLOAT] [--force_isize] [--frac_samp FLOAT] [--t INT] [--chunk_pairs INT] [--batch_pairs INT] [--device INT | --devices LIST] [--read_len INT] [--clean_names] [--strict_reference] [--host_reader] [--host_consumers]\n"
@@ -841,14 +842,20 @@ bool pick_devices(Run &R) {
 }
 // The writer of the run's BAM file: <out_prefix>.bam in input order, or with --sorted_bam <out_prefix>.sorted.bam in coordinate order with its index.
 int create_bam_file(const Args &A, const char *path, const fq_index_t *ix, const std::string &fai, const fq_qc_opts_t *qo, fq_bam_t **out) {
-  if (A.sorted_bam) return fq_bam_create_sorted(ix, fai.c_str(), path, A.rg.c_str(), qo, A.sort_mem, out);
-  return fq_bam_create(ix, fai.c_str(), path, A.rg.c_str(), qo, out);
+  const int rc = A.sorted_bam ? fq_bam_create_sorted(ix, fai.c_str(), path, A.rg.c_str(), qo, A.sort_mem, out) : fq_bam_create(ix, fai.c_str(), path, A.rg.c_str(), qo, out);
+  if (!rc && A.bam_deflate >= 0 && fq_bam_set_deflate(*out, A.bam_deflate)) die("--bam_deflate: the writer refused the mode");
+  return rc;
 }
 // ... and its close; a sorted writer says what it held and where the close's time went
 bool close_bam_file(const Args &A, fq_bam_t *bam) {
   fq_bam_sort_stats_t st{};
+  fq_bam_deflate_stats_t zs{};
   if (A.sorted_bam) fq_bam_sort_stats_at_close(bam, &st);
+  fq_bam_deflate_stats_at_close(bam, &zs);
   if (fq_bam_close(bam)) return false;
+  if (zs.mode == FQ_DEFLATE_DYNAMIC)
+    fprintf(stderr, "NOTICE - BAM writer: deflate mode dynamic (block type chosen per member): %lld of the device's members took dynamic Huffman tables, %lld the fixed code\n", (long long)zs.members_dynamic, (long long)zs.members_fixed);
+  else fprintf(stderr, "NOTICE - BAM writer: deflate mode fixed (one fixed-Huffman block per member of the device)\n");
   if (A.sorted_bam) {
     fprintf(stderr, "NOTICE - sorted BAM: %lld records in %lld runs (%lld sorted on the device inside their calls, %lld spilled to files); keys of %d bits\n", (long long)st.records, (long long)st.runs,
             (long long)st.device_sorted_runs, (long long)st.spilled_runs, st.key_bits);
@@ -1050,6 +1057,10 @@ int main(int argc, char **argv) {
     else if (f == "--host_reader") A.host_reader = true;
     else if (f == "--host_consumers") A.host_consumers = true;
     else if (f == "--sorted_bam") A.sorted_bam = true;
+    else if (f == "--bam_deflate") {
+      const std::string m = need("");
+      if (m == "fixed") A.bam_deflate = FQ_DEFLATE_FIXED; else if (m == "dynamic") A.bam_deflate = FQ_DEFLATE_DYNAMIC; else die("--bam_deflate takes fixed or dynamic, not " + m);
+    }
     else if (f == "--sort_mem") { A.sort_mem = atoll(need("")); if (A.sort_mem < 0) die("--sort_mem must not be negative"); }
     else if (f == "--batch_pairs") A.o.batch_pairs = atoi(need(""));   // READ_BUFFER_SIZE of the run to reproduce (default 262144)
     else if (f == "--device") A.device = atoi(need(""));
@@ -1070,6 +1081,7 @@ int main(int argc, char **argv) {
   // read filter looks at, and the re-allocation is invisible; a smaller --read_len would make it visible, and is refused.
   if (A.read_len < 96) die("--read_len must be at least 96 (the reference's is 151): below that its slot re-allocation (src/BwtMapper.cpp:536-546) would show in the read filter, and it is not modelled");
   if (A.sorted_bam && A.sam_out) die("--sorted_bam writes a BAM file: it cannot be combined with --sam_out (sorting the SAM text is not supported)");
+  if (A.bam_deflate >= 0 && A.sam_out) die("--bam_deflate chooses how the BAM file is compressed: it cannot be combined with --sam_out");
   if (A.collate && A.bam_in.empty()) die("--collate finds the mates of a BAM file: it needs --bam_in");
   if (A.collate_mem_given && !A.collate) die("--collate_mem bounds what --collate holds: it needs --collate");
   if (A.out_prefix == "Empty") die("--out_prefix is required");

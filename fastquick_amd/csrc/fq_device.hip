@@ -1612,6 +1612,23 @@ __global__ void __launch_bounds__(256) k_bgzf_deflate(FqDeflateArgs a) {
   const uint32_t bs = fqd_member(a, b, lds[threadIdx.x >> 6]);
   if ((threadIdx.x & 63) == 0) a.bsize[b] = bs;
 }
+// ... with the block type chosen per member (fqd_member_dyn)
+__global__ void __launch_bounds__(256, 7) k_bgzf_deflate_dyn(FqDeflateArgs a) {      // (seven wavefronts a SIMD: what its LDS allows)
+  __shared__ FqdDynLds lds[4];
+  const uint32_t b = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (b >= a.n_blocks) return;
+  const uint32_t bs = fqd_member_dyn(a, b, lds[threadIdx.x >> 6]);
+  if ((threadIdx.x & 63) == 0) a.bsize[b] = bs;
+}
+// fqd_code_lengths alone, by one wavefront (tests)
+__global__ void __launch_bounds__(64) k_code_lengths(const uint32_t *freq, int n_sym, int limit, uint8_t *len) {
+  __shared__ FqdHuff w;
+  __shared__ uint32_t f[FQD_MAX_SYMS];
+  __shared__ uint8_t l[FQD_MAX_SYMS];
+  for (int s = (int)threadIdx.x; s < n_sym; s += 64) f[s] = freq[s];
+  fqd_code_lengths(f, n_sym, limit, l, w);
+  for (int s = (int)threadIdx.x; s < n_sym; s += 64) len[s] = l[s];
+}
 __global__ void __launch_bounds__(256) k_bgzf_pack(FqDeflatePackArgs a, uint64_t n) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t < n) fqd_pack_piece(a, t);
@@ -1622,6 +1639,22 @@ int launch_deflate(const FqDeflateArgs &a) {
   hipEvent_t e0, e1;
   kernel_events(FQ_K_EMIT, &e0, &e1);
   hipExtLaunchKernelGGL(k_bgzf_deflate, dim3(nblk(a.n_blocks, 4)), dim3(256), 0, g_stream, e0, e1, 0, a);
+  FQ_HIP(hipGetLastError());
+  return 0;
+}
+int launch_deflate_dyn(const FqDeflateArgs &a) {
+  FQ_PRE();
+  if (!a.n_blocks) return 0;
+  if (!a.tok) { g_err = "BGZF members, dynamic mode: no room for the tokens"; return -1; }
+  hipEvent_t e0, e1;
+  kernel_events(FQ_K_EMIT, &e0, &e1);
+  hipExtLaunchKernelGGL(k_bgzf_deflate_dyn, dim3(nblk(a.n_blocks, 4)), dim3(256), 0, g_stream, e0, e1, 0, a);
+  FQ_HIP(hipGetLastError());
+  return 0;
+}
+int launch_code_lengths(const uint32_t *freq, int n_sym, int limit, uint8_t *len) {
+  FQ_PRE();
+  hipLaunchKernelGGL(k_code_lengths, dim3(1), dim3(64), 0, g_stream, freq, n_sym, limit, len);
   FQ_HIP(hipGetLastError());
   return 0;
 }

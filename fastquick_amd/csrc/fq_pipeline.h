@@ -185,6 +185,7 @@ const FqBamCallOut *fq_ctx_bam_out(const fq_ctx_t *c);
 int fq_bam_device_prepare(fq_bam *b, FqBamArgs *a);
 int64_t fq_ctx_bam_stream(fq_ctx_t *c, fq_sink_fn sink, void *user, int what);   // what: FQ_BAM_STREAM_* (the raw records in input order, their BGZF members, a sorted call's records or entries)
 bool fq_bam_wants_members(const fq_bam *b);
+int fq_bam_deflate_mode(const fq_bam *b);      // FQ_DEFLATE_*: which launcher makes the members
 int fq_qc_device_prepare(fq_qc *q, FqQcArgs *a, int n_surv);
 // the counting steps of calls that share a consumer run one at a time, in the order in which the calls passed their order-dependent part
 uint64_t fq_qc_gate_ticket(fq_qc *q);

@@ -509,6 +509,27 @@ int fq_ctx_attach_bam(fq_ctx_t *c, fq_bam_t *b);
  * block, CRC-32 -- csrc/fq_deflate.h), the members behind each other in out; replaces the zlib deflate of the reference's BGZF layer
  * (VerifyBamID/statgen/BgzfFileType.h over htslib's bgzf_write) for the records a context with a writer attached formats on the device. */
 int fq_bgzf_deflate_device(int device, const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int64_t *out_len, double *kernel_ms);
+/* How the device compresses the members of a writer's file (the choice htslib's bgzf_write leaves to zlib's deflate: the block type).
+ * FQ_DEFLATE_FIXED (the default): one fixed-Huffman block per member, as above.  FQ_DEFLATE_DYNAMIC: the same greedy parse, its tokens kept and
+ * counted, and per member the block type that costs fewer bits -- BTYPE = 10 with code lengths made from the counts (at most 15 bits, 7 for the
+ * code-length code, every code complete, never fewer than two codes in an alphabet), or the fixed block where the tables would not pay; a member of
+ * this mode is never larger than the fixed encoding of its parse.  What a file inflates to does not depend on the mode.
+ * fq_bam_set_deflate: FQ_EINVAL for another value, or once the writer has taken records.  Without the call the mode comes from the environment
+ * (FASTQUICK_BAM_DEFLATE=dynamic|fixed); the call wins.  FASTQUICK_BAM_HOST_DEFLATE=1 (zlib on the host, dynamic by itself) goes before either.
+ * fq_bam_deflate_stats: the mode, and in dynamic mode how many of the device's members took each block type so far; fq_bam_deflate_stats_at_close
+ * registers a struct that fq_bam_close fills in with the final counts (the close frees the writer; a sorted writer compresses there). */
+#define FQ_DEFLATE_FIXED 0
+#define FQ_DEFLATE_DYNAMIC 1
+typedef struct { int32_t mode; int64_t members_fixed, members_dynamic; } fq_bam_deflate_stats_t;
+int fq_bam_set_deflate(fq_bam_t *b, int mode);
+int fq_bam_deflate_stats(const fq_bam_t *b, fq_bam_deflate_stats_t *out);
+int fq_bam_deflate_stats_at_close(fq_bam_t *b, fq_bam_deflate_stats_t *out);
+/* (tests, tools) fq_bgzf_deflate_device in the given mode (FQ_DEFLATE_FIXED: the same bytes as that entry), and the code lengths alone: len_out[s] for
+ * the n_sym frequencies (2..288 of them, limit 1..15 with n_sym <= 2^limit, the sum below 2^32), made by one wavefront -- 0 for a symbol of
+ * frequency 0, except the one or two that the two-codes rule hands a one-bit code when fewer than two symbols are used.  Replaces zlib's
+ * build_tree / gen_bitlen behind the reference's BGZF layer. */
+int fq_bgzf_deflate_device_mode(int device, int mode, const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int64_t *out_len, double *kernel_ms);
+int fq_huffman_lengths_device(int device, const uint32_t *freq, int n_sym, int limit, uint8_t *len_out);
 /* ---- coordinate-sorted BAM with its index ----------------------------------------------------------------------------------
  * Replaces the two steps the pipeline runs on O.bam before pop+con reads it (bin/FASTQuick_template.sh:501-502: `samtools sort -O BAM O.bam >
  * O.sorted.bam`, `samtools index O.sorted.bam`).  The writer fq_bam_create_sorted returns takes records as every fq_bam_t does (fq_ctx_attach_bam,
