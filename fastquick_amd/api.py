@@ -96,7 +96,8 @@ class FrontEndStats(C.Structure):
                 ("ms_wait_reader", C.c_double), ("ms_wait_slot", C.c_double), ("ms_read", C.c_double), ("ms_upload", C.c_double),
                 ("bam_records", C.c_int64), ("bam_skipped", C.c_int64), ("chain_repairs", C.c_int64), ("ms_transcode", C.c_double),
                 ("ms_bam_starts", C.c_double), ("ms_bam_pairs", C.c_double), ("ms_bam_fill", C.c_double),
-                ("bam_orphans", C.c_int64), ("bam_held_peak_records", C.c_int64), ("bam_held_peak_bytes", C.c_int64), ("ms_bam_collate", C.c_double)]
+                ("bam_orphans", C.c_int64), ("bam_held_peak_records", C.c_int64), ("bam_held_peak_bytes", C.c_int64), ("ms_bam_collate", C.c_double),
+                ("bam_unselected", C.c_int64), ("bam_oq_records", C.c_int64), ("ms_bam_tags", C.c_double), ("bam_empty_chunks", C.c_int64)]
 
 
 class BamCollate(C.Structure):      # fq_bam_collate_t
@@ -110,6 +111,14 @@ class BamCollate(C.Structure):      # fq_bam_collate_t
 class BamProbe(C.Structure):      # fq_bam_probe_t
     _fields_ = [("n_ref", C.c_int32), ("paired", C.c_int32), ("first_flag", C.c_int32), ("first_l_seq", C.c_int32), ("first_l_name", C.c_int32), ("has_eof_block", C.c_int32),
                 ("header_bytes", C.c_int64), ("rec_member_off", C.c_int64), ("rec_off", C.c_int64), ("sort_order", C.c_char * 32), ("error", C.c_char * 256)]
+
+
+class BamSelect(C.Structure):      # fq_bam_select_t
+    _fields_ = [("ids", C.POINTER(C.c_char_p)), ("n_ids", C.c_int32), ("use_oq", C.c_int32)]
+
+
+class BamTagCounts(C.Structure):      # fq_bam_tag_counts_t
+    _fields_ = [("unselected", C.c_int64), ("oq_records", C.c_int64), ("ms_tags", C.c_double)]
 
 
 class BamTranscode(C.Structure):      # fq_bam_transcode_t
@@ -129,6 +138,7 @@ EXPORTS = ["fq_default_opts", "fq_index_build", "fq_index_load", "fq_index_destr
            "fq_fastq_open", "fq_fastq_configure", "fq_fastq_set_sampling", "fq_fastq_read", "fq_fastq_last_error", "fq_fastq_dropped_record", "fq_fastq_unequal_lengths", "fq_fastq_is_bgzf", "fq_fastq_close", "fq_inflate_raw", "fq_crc32", "fq_inflate_device", "fq_bgzf_inflate_device",
            "fq_frontend_open", "fq_frontend_next", "fq_frontend_release", "fq_frontend_handover", "fq_frontend_unequal_lengths", "fq_frontend_stats", "fq_frontend_last_error", "fq_frontend_close",
            "fq_text_batch_pairs", "fq_text_batch_first_name", "fq_align_text", "fq_text_batch_fetch", "fq_bam_probe", "fq_frontend_open_bam", "fq_bam_transcode_device", "fq_frontend_open_bam_collate", "fq_bam_collate_device",
+           "fq_bam_probe_select", "fq_bam_read_groups", "fq_frontend_open_bam_select", "fq_frontend_open_bam_collate_select", "fq_bam_transcode_device_select", "fq_bam_collate_device_select",
            "fq_ctx_set_emit", "fq_sam_device_last", "fq_sam_device_bytes", "fq_ctx_attach_qc", "fq_ctx_attach_bam", "fq_bgzf_deflate_device", "fq_bgzf_deflate_device_mode", "fq_huffman_lengths_device", "fq_bam_set_deflate", "fq_bam_deflate_stats",
            "fq_bam_create_sorted", "fq_bam_sort_stats", "fq_bam_sort_stats_at_close", "fq_bam_sort_run_entries", "fq_sort_keys_device"]
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)
@@ -221,6 +231,12 @@ def load_library(path: str | None = None):
                                         C.c_size_t, C.POINTER(BamCollate)]
     L.fq_bam_transcode_device.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                           C.c_void_p, C.c_int64, C.POINTER(BamTranscode)]
+    L.fq_bam_probe_select.argtypes = [C.c_char_p, C.POINTER(BamSelect), C.POINTER(BamProbe)]
+    L.fq_bam_read_groups.argtypes = [C.c_char_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    L.fq_frontend_open_bam_select.argtypes = L.fq_frontend_open_bam.argtypes[:-1] + [C.POINTER(BamSelect), C.POINTER(C.c_void_p)]
+    L.fq_frontend_open_bam_collate_select.argtypes = L.fq_frontend_open_bam_collate.argtypes[:-1] + [C.POINTER(BamSelect), C.POINTER(C.c_void_p)]
+    L.fq_bam_transcode_device_select.argtypes = L.fq_bam_transcode_device.argtypes[:-1] + [C.POINTER(BamSelect), C.POINTER(BamTagCounts), C.POINTER(BamTranscode)]
+    L.fq_bam_collate_device_select.argtypes = L.fq_bam_collate_device.argtypes[:-1] + [C.POINTER(BamSelect), C.POINTER(BamTagCounts), C.POINTER(BamCollate)]
     L.fq_frontend_next.restype = C.c_int64
     L.fq_frontend_next.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.fq_frontend_release.restype = None
@@ -882,14 +898,40 @@ def bgzf_inflate_device(blob: bytes, text_cap: int, device: int = 0, lib=None, r
 
 
 FQ_EFALLBACK = -6
-BAM_BAD_KINDS = {0: None, 1: "mixed", 2: "l_seq0", 3: "fields", 4: "name", 5: "mates", 6: "names", 7: "dup"}      # fq_bam_transcode_t::bad_kind, fq_bam_collate_t::bad_kind
+BAM_BAD_KINDS = {0: None, 1: "mixed", 2: "l_seq0", 3: "fields", 4: "name", 5: "mates", 6: "names", 7: "dup", 8: "aux", 9: "oq"}      # fq_bam_transcode_t::bad_kind, fq_bam_collate_t::bad_kind
 
 
-def bam_probe(path: str, lib=None) -> dict:
-    """fq_bam_probe: the host's look at a BAM file (header, first kept record).  Raises FastquickError with the library's message."""
+def bam_select(rg=(), oq: bool = False):
+    """fq_bam_select_t for the _select entries (the IDs as str or bytes), or None where nothing is asked for: the caller then takes the entry without _select"""
+    ids = [x if isinstance(x, bytes) else x.encode() for x in (rg or ())]
+    if not ids and not oq:
+        return None
+    arr = (C.c_char_p * max(len(ids), 1))(*ids)
+    sel = BamSelect(C.cast(arr, C.POINTER(C.c_char_p)), len(ids), 1 if oq else 0)
+    sel._keep = arr
+    return sel
+
+
+def bam_read_groups(path: str, lib=None) -> list:
+    """fq_bam_read_groups: the ID values of the header's @RG lines, in the header's order"""
+    L = lib or load_library()
+    n, nb = C.c_int32(), C.c_int64()
+    rc = L.fq_bam_read_groups(path.encode(), None, 0, C.byref(n), C.byref(nb))
+    if rc not in (0, -5):
+        raise FastquickError("fq_bam_read_groups failed: %d" % rc)
+    buf = C.create_string_buffer(max(nb.value, 1))
+    if nb.value and L.fq_bam_read_groups(path.encode(), buf, nb.value, C.byref(n), C.byref(nb)):
+        raise FastquickError("fq_bam_read_groups failed")
+    return [x.decode(errors="replace") for x in buf.raw[:nb.value].split(b"\0")[:n.value]]
+
+
+def bam_probe(path: str, lib=None, rg=(), oq: bool = False) -> dict:
+    """fq_bam_probe: the host's look at a BAM file (header, first kept record; with rg: the first kept record under the selection, fq_bam_probe_select).
+    Raises FastquickError with the library's message."""
     L = lib or load_library()
     pr = BamProbe()
-    rc = L.fq_bam_probe(path.encode(), C.byref(pr))
+    sel = bam_select(rg, oq)
+    rc = L.fq_bam_probe_select(path.encode(), C.byref(sel), C.byref(pr)) if sel is not None else L.fq_bam_probe(path.encode(), C.byref(pr))
     if rc:
         raise FastquickError(pr.error.decode(errors="replace") or "fq_bam_probe failed: %d" % rc)
     d = {k: getattr(pr, k) for k, _ in BamProbe._fields_ if k not in ("error", "sort_order")}
@@ -897,9 +939,9 @@ def bam_probe(path: str, lib=None) -> dict:
     return d
 
 
-def bam_transcode_device(payload: bytes, member_off, n_ref: int, first_record: int = 0, paired: int = -1, device: int = 0, lib=None) -> dict:
+def bam_transcode_device(payload: bytes, member_off, n_ref: int, first_record: int = 0, paired: int = -1, device: int = 0, lib=None, rg=(), oq: bool = False) -> dict:
     """fq_bam_transcode_device: BAM records of a payload -> (text1, text2, record starts, counts, first refusal, chain_repairs); the members begin
-    at member_off (the cuts of the boundary search)."""
+    at member_off (the cuts of the boundary search).  rg / oq: fq_bam_transcode_device_select, with `unselected`, `oq_records` and `ms_tags` in the result."""
     L = lib or load_library()
     buf = np.frombuffer(bytes(payload) + b"\0", dtype=np.uint8)
     n = len(payload)
@@ -908,11 +950,18 @@ def bam_transcode_device(payload: bytes, member_off, n_ref: int, first_record: i
     t1, t2 = np.zeros(cap, dtype=np.uint8), np.zeros(cap, dtype=np.uint8)
     st = np.zeros(n // 36 + 2, dtype=np.uint32)
     out = BamTranscode()
-    rc = L.fq_bam_transcode_device(device, buf.ctypes.data, n, mo.ctypes.data if mo.size else None, mo.size, n_ref, first_record, paired,
-                                   t1.ctypes.data, cap, t2.ctypes.data, cap, st.ctypes.data, st.size, C.byref(out))
+    sel, cnt = bam_select(rg, oq), BamTagCounts()
+    if sel is not None:
+        rc = L.fq_bam_transcode_device_select(device, buf.ctypes.data, n, mo.ctypes.data if mo.size else None, mo.size, n_ref, first_record, paired,
+                                              t1.ctypes.data, cap, t2.ctypes.data, cap, st.ctypes.data, st.size, C.byref(sel), C.byref(cnt), C.byref(out))
+    else:
+        rc = L.fq_bam_transcode_device(device, buf.ctypes.data, n, mo.ctypes.data if mo.size else None, mo.size, n_ref, first_record, paired,
+                                       t1.ctypes.data, cap, t2.ctypes.data, cap, st.ctypes.data, st.size, C.byref(out))
     if rc:
         raise FastquickError("fq_bam_transcode_device failed: %d" % rc)
     d = {k: getattr(out, k) for k, _ in BamTranscode._fields_ if k != "text_len"}
+    if sel is not None:
+        d.update({k: getattr(cnt, k) for k, _ in BamTagCounts._fields_})
     d["bad_kind"] = BAM_BAD_KINDS.get(out.bad_kind, out.bad_kind)
     d["text1"] = t1[:out.text_len[0]].tobytes() if out.bad_record < 0 else None
     d["text2"] = t2[:out.text_len[1]].tobytes() if out.bad_record < 0 else None
@@ -921,7 +970,7 @@ def bam_transcode_device(payload: bytes, member_off, n_ref: int, first_record: i
 
 
 def bam_collate_device(payload: bytes, member_off, n_ref: int, first_record: int = 0, members_per_chunk: int = 0, collate_mem: int = 4 << 30, paired: int = -1, device: int = 0,
-                       lib=None) -> dict:
+                       lib=None, rg=(), oq: bool = False) -> dict:
     """fq_bam_collate_device: the collating chunk loop on a payload -> (text1, text2, counts, orphans, held peak, first refusal, device ms by kernel);
     members_per_chunk members a chunk (0: one chunk).  Raises FastquickError with the library's message (--collate_mem exceeded: code -5)."""
     L = lib or load_library()
@@ -933,14 +982,21 @@ def bam_collate_device(payload: bytes, member_off, n_ref: int, first_record: int
     t1[cap:] = 0xa5
     t2[cap:] = 0xa5
     out = BamCollate()
-    rc = L.fq_bam_collate_device(device, buf.ctypes.data, n, mo.ctypes.data if mo.size else None, mo.size, members_per_chunk, n_ref, first_record, paired, collate_mem,
-                                 t1.ctypes.data, cap, t2.ctypes.data, cap, C.byref(out))
+    sel, cnt = bam_select(rg, oq), BamTagCounts()
+    if sel is not None:      # (fq_bam_collate_device_select: `unselected`, `oq_records` and `ms_tags` join the result)
+        rc = L.fq_bam_collate_device_select(device, buf.ctypes.data, n, mo.ctypes.data if mo.size else None, mo.size, members_per_chunk, n_ref, first_record, paired, collate_mem,
+                                            t1.ctypes.data, cap, t2.ctypes.data, cap, C.byref(sel), C.byref(cnt), C.byref(out))
+    else:
+        rc = L.fq_bam_collate_device(device, buf.ctypes.data, n, mo.ctypes.data if mo.size else None, mo.size, members_per_chunk, n_ref, first_record, paired, collate_mem,
+                                     t1.ctypes.data, cap, t2.ctypes.data, cap, C.byref(out))
     assert (t1[cap:] == 0xa5).all() and (t2[cap:] == 0xa5).all(), "fq_bam_collate_device wrote behind a text buffer"
     if rc:
         e = FastquickError("fq_bam_collate_device failed: %d (%s)" % (rc, out.error.decode(errors="replace")))
         e.code = rc
         raise e
     d = {k: getattr(out, k) for k, _ in BamCollate._fields_ if k not in ("text_len", "error")}
+    if sel is not None:
+        d.update({k: getattr(cnt, k) for k, _ in BamTagCounts._fields_})
     d["bad_kind"] = BAM_BAD_KINDS.get(out.bad_kind, out.bad_kind)
     d["text1"] = t1[:out.text_len[0]].tobytes() if out.bad_record < 0 else None
     d["text2"] = t2[:out.text_len[1]].tobytes() if out.bad_record < 0 else None
@@ -1053,12 +1109,17 @@ class BamFrontEnd(DeviceFrontEnd):
     _open_name = "fq_frontend_open_bam"
 
     def __init__(self, bam: str, batch_pairs: int = 262144, chunk_pairs: int = 16 * 262144, slot_mode: int = 0, max_read_len: int = 160, device: int = 0, lib=None,
-                 collate_mem: int | None = None):
+                 collate_mem: int | None = None, rg=(), oq: bool = False):
         bam_probe(bam, lib=lib)      # (its message, where the file is refused)
+        self.sel = bam_select(rg, oq)      # read groups to select / OQ for the quality line (the _select entries); None: neither
         self.collate_mem = collate_mem      # bytes: mates are found by name (fq_frontend_open_bam_collate); None: they are adjacent
         super().__init__(bam, None, batch_pairs, chunk_pairs, slot_mode, max_read_len, device, lib)
 
     def _open(self, device, bam, _fq2, batch_pairs, chunk_pairs, slot_mode, max_read_len):
+        if self.sel is not None and self.collate_mem is not None:
+            return self.L.fq_frontend_open_bam_collate_select(device, bam.encode(), batch_pairs, chunk_pairs, slot_mode, max_read_len, self.collate_mem, C.byref(self.sel), C.byref(self.h))
+        if self.sel is not None:
+            return self.L.fq_frontend_open_bam_select(device, bam.encode(), batch_pairs, chunk_pairs, slot_mode, max_read_len, C.byref(self.sel), C.byref(self.h))
         if self.collate_mem is not None:
             return self.L.fq_frontend_open_bam_collate(device, bam.encode(), batch_pairs, chunk_pairs, slot_mode, max_read_len, self.collate_mem, C.byref(self.h))
         return self.L.fq_frontend_open_bam(device, bam.encode(), batch_pairs, chunk_pairs, slot_mode, max_read_len, C.byref(self.h))

@@ -20,6 +20,9 @@
 //                       stably by hash (fq_sort.h); a thread per run of equal hashes walks it in ordinal order and applies the serial definition
 //                        among byte-equal names; a scan over the completing records gives the pairs their places; after the fill the
 //                       records still waiting are gathered, a wavefront each, into the other half of the held store
+//   (b'') tags          (`--bam_rg`, `--bam_oq`; in place of (b)'s keep) a thread per record walks the auxiliary fields (SAM specification 4.2.4): kept is
+//                       then "neither secondary nor supplementary, and its RG:Z is one of the wanted IDs"; where OQ:Z is to be read, its offset in the
+//                       record goes with the record -- to its unit, and into the held store -- and the fill takes the quality line from there
 #pragma once
 #include <stdint.h>
 #include <stdlib.h>
@@ -31,8 +34,9 @@
 #define FQB_MAX_BLOCK (1u << 28)          // a block_size (or l_seq) above this is not a record's
 #define FQB_MAX_REPAIRS 64                // relaunches of a member's walk in one chunk; then the serial walk
 enum { FQB_SEG_OK = 0, FQB_SEG_CUT = 1, FQB_SEG_CORRUPT = 2 };      // how a member's walk ended: at the member's end; at a record the payload's end cuts off; at a block_size that is none
-// what a record is refused for; a refusal is the pair (record ordinal, kind) as ordinal << 3 | kind, and the stream's is the smallest
-enum { FQB_BAD_MIXED = 1, FQB_BAD_LSEQ0 = 2, FQB_BAD_FIELDS = 3, FQB_BAD_NAME = 4, FQB_BAD_MATES = 5, FQB_BAD_NAMES = 6, FQB_BAD_DUP = 7 };
+// what a record is refused for; a refusal is the pair (record ordinal, kind) as ordinal << FQB_KIND_BITS | kind, and the stream's is the smallest
+enum { FQB_BAD_MIXED = 1, FQB_BAD_LSEQ0 = 2, FQB_BAD_FIELDS = 3, FQB_BAD_NAME = 4, FQB_BAD_MATES = 5, FQB_BAD_NAMES = 6, FQB_BAD_DUP = 7, FQB_BAD_AUX = 8, FQB_BAD_OQ = 9 };
+#define FQB_KIND_BITS 4
 #define FQB_NO_BAD 0xffffffffffffffffull
 
 // seg[0 .. n_seg]: where the members begin in the payload (seg[0]: the first record; seg[n_seg] = n); per member: first (where its walk began, or
@@ -48,10 +52,19 @@ struct FqBamPairArgs {
   uint32_t n_units; int32_t paired; uint64_t ord0;             // units: pairs, or single records; ord0: the stream's records in front of this chunk's
   uint32_t *src[2], *len[2];                                   // per unit and side: the record's offset, its text's length
   uint64_t *bad;
+  const uint32_t *roq; uint32_t *oq[2];                        // (--bam_oq; or null) per record: the offset of its OQ value in the record, 0: none; per unit and side: the same
+};
+// (b'') sel (or null: every record is selected): the wanted IDs as dwords -- their count, their lengths, then their bytes one behind the other
+struct FqBamTagArgs {
+  const uint8_t *pay; const uint32_t *starts; uint32_t n_rec; uint64_t ord0;
+  const uint32_t *sel; int32_t use_oq;
+  uint32_t *kept, *roq, *unsel, *hasoq;                        // per record: kept 0/1; the OQ value's offset (0: none, or not asked for); not selected 0/1; kept with an OQ value 0/1
+  uint64_t *bad;
 };
 // from[e] (collation; or null): per unit, 1 where side e's record lies in the held store -- src[e][u] is then its index there, held + hoff[index] the record
 struct FqBamFillArgs { const uint8_t *pay; const uint32_t *src[2]; const uint64_t *off[2]; uint8_t *text[2]; uint32_t n_units; int32_t n_sides; uint64_t total[2];      // total[e] = off[e][n_units]
-                       const uint8_t *held; const uint64_t *hoff; const uint8_t *from[2]; };
+                       const uint8_t *held; const uint64_t *hoff; const uint8_t *from[2];
+                       const uint32_t *oq[2]; };      // oq[e] (--bam_oq; or null): per unit, the offset of the OQ value in side e's record, 0: none
 // Collation.  Candidates of a chunk: the held records [0, n_held) -- older, in ordinal order -- then the chunk's kept records in chunk order.
 enum { FQC_WAIT = 0, FQC_PAIR = 1, FQC_USED = 2, FQC_BAD = 3 };      // a candidate: waits for its mate; completes a pair with mate[c]; is the earlier record of a pair; is refused
 struct FqBamCollateArgs {
@@ -66,6 +79,7 @@ struct FqBamCollateArgs {
   uint64_t *bad;
   uint32_t *surv, *rlen; const uint64_t *sidx, *soff;                                      // per candidate: still waiting; its bytes; their scans
   uint8_t *nheld; uint64_t *noff, *nkey, *nord;                                            // the other half of the held store
+  const uint32_t *roq, *hoq; uint32_t *oq[2], *noq;                                        // (--bam_oq; or all null) the OQ offsets: per record of the chunk, per held record; per unit and side; of the other half
 };
 
 FQ_HD uint32_t fqb_ld16(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
@@ -133,7 +147,9 @@ FQ_HD void fq_bam_chain_serial(const FqBamChainArgs &a, uint32_t k, uint32_t p) 
 // ---- (b) ----
 FQ_HD void fq_bam_keep_thread(const FqBamPairArgs &a, uint32_t i) { a.kept[i] = (fqb_ld16(a.pay + a.starts[i] + 18) & 0x900u) ? 0u : 1u; }
 FQ_HD void fq_bam_kidx_thread(const FqBamPairArgs &a, uint32_t i) { if (a.kept[i]) a.kidx[a.kord[i]] = i; }
-FQ_HD uint64_t fqb_bad(uint64_t ord, uint32_t kind) { return ord << 3 | kind; }
+FQ_HD uint64_t fqb_bad(uint64_t ord, uint32_t kind) { return ord << FQB_KIND_BITS | kind; }
+FQ_HD uint64_t fqb_bad_ord(uint64_t bad) { return bad >> FQB_KIND_BITS; }
+FQ_HD uint32_t fqb_bad_kind(uint64_t bad) { return (uint32_t)(bad & ((1u << FQB_KIND_BITS) - 1u)); }
 FQ_HD uint64_t fqb_min64(uint64_t x, uint64_t y) { return x < y ? x : y; }
 // what one kept record is refused for on its own (FQB_NO_BAD: nothing)
 FQ_HD uint64_t fq_bam_record_check(const uint8_t *r, uint64_t ord, int32_t paired) {
@@ -152,6 +168,7 @@ FQ_HD uint64_t fq_bam_unit_thread(const FqBamPairArgs &a, uint32_t u) {
     const uint32_t i = a.kidx[u], s = a.starts[i];
     const uint64_t bad = fq_bam_record_check(a.pay + s, a.ord0 + i, 0);
     a.src[0][u] = s; a.len[0][u] = bad == FQB_NO_BAD ? fq_bam_text_len(a.pay + s) : 0;
+    if (a.roq) a.oq[0][u] = a.roq[i];
     return bad;
   }
   const uint32_t ia = a.kidx[2 * u], ib = a.kidx[2 * u + 1], sa = a.starts[ia], sb = a.starts[ib];
@@ -166,14 +183,93 @@ FQ_HD uint64_t fq_bam_unit_thread(const FqBamPairArgs &a, uint32_t u) {
     if (!same) bad = fqb_bad(a.ord0 + ia, FQB_BAD_NAMES);
   }
   a.src[0][u] = a_first ? sa : sb; a.src[1][u] = a_first ? sb : sa;
+  if (a.roq) { a.oq[0][u] = a.roq[a_first ? ia : ib]; a.oq[1][u] = a.roq[a_first ? ib : ia]; }
   a.len[0][u] = bad == FQB_NO_BAD ? fq_bam_text_len(a_first ? ra : rb) : 0;
   a.len[1][u] = bad == FQB_NO_BAD ? fq_bam_text_len(a_first ? rb : ra) : 0;
   return bad;
 }
 
+// ---- (b'') ----
+// The auxiliary fields of record r, which lies whole in the payload: from behind the qualities to 4 + block_size, a field after the other -- two tag
+// bytes, a type, a value (A c C: 1 byte; s S: 2; i I f: 4; Z H: up to and including the first NUL inside the area; B: a subtype of cCsSiIf, a 32-bit
+// count, count x size bytes, in 64 bits).  The first RG and the first OQ are noted: the value's offset in the record and its length without the
+// NUL.  False (FQB_BAD_AUX) unless the walk ends exactly at the area's end: an unknown type or subtype, a value that runs beyond the area, a Z / H
+// without NUL, one or two stray bytes, a first RG or OQ whose type is not Z.  Every step moves on by three bytes at least and reads inside the area only.
+struct FqBamAux { uint32_t rg, rg_len, oq, oq_len; };      // (offset 0: the record has none)
+FQ_HD uint32_t fqb_aux_size(uint8_t t) { return t == 'A' || t == 'c' || t == 'C' ? 1u : t == 's' || t == 'S' ? 2u : t == 'i' || t == 'I' || t == 'f' ? 4u : 0u; }
+FQ_HD bool fq_bam_aux_walk(const uint8_t *r, FqBamAux *x) {
+  x->rg = x->rg_len = x->oq = x->oq_len = 0;
+  const uint64_t end = 4ull + fqb_ld32(r);
+  uint64_t p = 4ull + fqb_min_block(r[12], fqb_ld16(r + 16), fqb_ld32(r + 20));
+  if (p > end) return false;
+  while (p < end) {
+    if (p + 3 > end) return false;
+    const uint8_t t0 = r[p], t1 = r[p + 1], ty = r[p + 2];
+    const bool is_rg = t0 == 'R' && t1 == 'G' && !x->rg, is_oq = t0 == 'O' && t1 == 'Q' && !x->oq;
+    if ((is_rg || is_oq) && ty != 'Z') return false;
+    p += 3;
+    if (ty == 'Z' || ty == 'H') {
+      uint64_t q = p;
+      while (q < end && r[q]) ++q;
+      if (q >= end) return false;
+      if (is_rg) { x->rg = (uint32_t)p; x->rg_len = (uint32_t)(q - p); }
+      if (is_oq) { x->oq = (uint32_t)p; x->oq_len = (uint32_t)(q - p); }
+      p = q + 1;
+    } else if (ty == 'B') {
+      if (p + 5 > end) return false;
+      const uint64_t sz = fqb_aux_size(r[p]);
+      if (!sz || r[p] == 'A') return false;
+      p += 5 + sz * (uint64_t)fqb_ld32(r + p + 1);
+    } else {
+      const uint32_t sz = fqb_aux_size(ty);
+      if (!sz) return false;
+      p += sz;
+    }
+    if (p > end) return false;
+  }
+  return true;
+}
+// is the value one of the wanted IDs, in length and in bytes?
+FQ_HD bool fq_bam_rg_wanted(const uint32_t *sel, const uint8_t *v, uint32_t len) {
+  const uint32_t n = sel[0];
+  const uint8_t *b = (const uint8_t *)(sel + 1 + n);
+  for (uint32_t k = 0; k < n; b += sel[1 + k], ++k) {
+    if (sel[1 + k] != len) continue;
+    uint32_t j = 0;
+    while (j < len && b[j] == v[j]) ++j;
+    if (j == len) return true;
+  }
+  return false;
+}
+// a record that is neither secondary nor supplementary, walked: selected or not, where its OQ value lies, whether that fits the read.  *kept, *oq (0: none,
+// or not asked for), *unsel as FqBamTagArgs has them per record.  Where the walk fails, the RG it met in front of what stopped it says selected or not: a
+// selected record stays kept, and its own check may refuse it for less.
+FQ_HD uint32_t fq_bam_tags_record(const uint8_t *r, const uint32_t *sel, int use_oq, uint32_t *kept, uint32_t *oq, uint32_t *unsel) {
+  *oq = 0;
+  FqBamAux x;
+  const bool good = fq_bam_aux_walk(r, &x);
+  const bool selected = !sel || (x.rg && fq_bam_rg_wanted(sel, r + x.rg, x.rg_len));
+  *kept = selected ? 1u : 0u; *unsel = selected ? 0u : 1u;
+  if (!good) return FQB_BAD_AUX;
+  if (!selected) return 0;
+  if (use_oq && x.oq) {
+    if (x.oq_len != fqb_ld32(r + 20)) return FQB_BAD_OQ;
+    for (uint32_t j = 0; j < x.oq_len; ++j) if (r[x.oq + j] < 0x21 || r[x.oq + j] > 0x7e) return FQB_BAD_OQ;
+    *oq = x.oq;
+  }
+  return 0;
+}
+FQ_HD uint64_t fq_bam_tags_thread(const FqBamTagArgs &a, uint32_t i) {
+  const uint8_t *r = a.pay + a.starts[i];
+  uint32_t kept = 0, oq = 0, unsel = 0, kind = 0;
+  if (!(fqb_ld16(r + 18) & 0x900u)) kind = fq_bam_tags_record(r, a.sel, a.use_oq, &kept, &oq, &unsel);
+  a.kept[i] = kept; a.roq[i] = oq; a.unsel[i] = unsel; a.hasoq[i] = oq ? 1u : 0u;
+  return kind ? fqb_bad(a.ord0 + i, kind) : FQB_NO_BAD;
+}
+
 // ---- (c) ----
-// byte j of the record's four lines "@name\nSEQ\n+\nQUAL\n" (nm name bytes, l bases)
-FQ_HD uint8_t fq_bam_text_byte(const uint8_t *r, uint32_t nm, uint32_t l, uint32_t n_cig, bool rev, uint32_t j) {
+// byte j of the record's four lines "@name\nSEQ\n+\nQUAL\n" (nm name bytes, l bases); oq (or null): the record's OQ value, l bytes that are Phred+33 as they stand
+FQ_HD uint8_t fq_bam_text_byte(const uint8_t *r, uint32_t nm, uint32_t l, uint32_t n_cig, bool rev, uint32_t j, const uint8_t *oq) {
   if (j == 0) return '@';
   if (j <= nm) return r[36 + j - 1];
   j -= nm + 1;
@@ -190,6 +286,7 @@ FQ_HD uint8_t fq_bam_text_byte(const uint8_t *r, uint32_t nm, uint32_t l, uint32
   if (j == 2) return '\n';
   j -= 3;
   if (j < l) {
+    if (oq) return oq[rev ? l - 1 - j : j];
     const uint32_t q = (seq + (l + 1) / 2)[rev ? l - 1 - j : j];
     return (uint8_t)(q > 93u ? 126u : q + 33u);        // min(q + 33, 126) (bwaseqio.c:118); a missing quality (0xff) is '~' as well
   }
@@ -198,8 +295,9 @@ FQ_HD uint8_t fq_bam_text_byte(const uint8_t *r, uint32_t nm, uint32_t l, uint32
 // lane of the wavefront of (unit u, side e).  The text lies at any alignment: a lane takes an aligned dword of the destination a step, whole dwords
 // inside the record's text are stored as dwords (256 contiguous bytes a wavefront and step), the at most three bytes at either end as bytes.
 FQ_HD const uint8_t *fq_bam_fill_rec(const FqBamFillArgs &a, int e, uint32_t u) { return a.from[e] && a.from[e][u] ? a.held + a.hoff[a.src[e][u]] : a.pay + a.src[e][u]; }
+FQ_HD const uint8_t *fq_bam_fill_oq(const FqBamFillArgs &a, int e, uint32_t u, const uint8_t *r) { return a.oq[e] && a.oq[e][u] ? r + a.oq[e][u] : nullptr; }
 FQ_HD void fq_bam_fill_lane(const FqBamFillArgs &a, uint32_t u, int e, uint32_t lane) {
-  const uint8_t *r = fq_bam_fill_rec(a, e, u);
+  const uint8_t *r = fq_bam_fill_rec(a, e, u), *oq = fq_bam_fill_oq(a, e, u, r);
   const uint32_t nm = (uint32_t)r[12] - 1u, n_cig = fqb_ld16(r + 16), l = fqb_ld32(r + 20);
   const bool rev = (fqb_ld16(r + 18) & 0x10u) != 0;
   const uint64_t len = a.off[e][u + 1] - a.off[e][u];
@@ -210,10 +308,10 @@ FQ_HD void fq_bam_fill_lane(const FqBamFillArgs &a, uint32_t u, int e, uint32_t 
     if (j0 >= (int64_t)len) break;
     if (j0 >= 0 && (uint64_t)j0 + 4 <= len) {
       uint32_t v = 0;
-      for (uint32_t t = 0; t < 4; ++t) v |= (uint32_t)fq_bam_text_byte(r, nm, l, n_cig, rev, (uint32_t)j0 + t) << (8 * t);
+      for (uint32_t t = 0; t < 4; ++t) v |= (uint32_t)fq_bam_text_byte(r, nm, l, n_cig, rev, (uint32_t)j0 + t, oq) << (8 * t);
       *(uint32_t *)(d + j0) = v;
     } else {
-      for (int64_t j = j0 < 0 ? 0 : j0; j < j0 + 4 && j < (int64_t)len; ++j) d[j] = fq_bam_text_byte(r, nm, l, n_cig, rev, (uint32_t)j);
+      for (int64_t j = j0 < 0 ? 0 : j0; j < j0 + 4 && j < (int64_t)len; ++j) d[j] = fq_bam_text_byte(r, nm, l, n_cig, rev, (uint32_t)j, oq);
     }
   }
 }
@@ -232,11 +330,11 @@ FQ_HD void fq_bam_fill_piece(const FqBamFillArgs &a, int e, uint64_t t) {
   while (b < hi) {
     while (u + 1 < a.n_units && a.off[e][u + 1] <= b) ++u;
     const uint64_t uend = a.off[e][u + 1] < hi ? a.off[e][u + 1] : hi;
-    const uint8_t *r = fq_bam_fill_rec(a, e, u);
+    const uint8_t *r = fq_bam_fill_rec(a, e, u), *oq = fq_bam_fill_oq(a, e, u, r);
     const uint32_t nm = (uint32_t)r[12] - 1u, n_cig = fqb_ld16(r + 16), l = fqb_ld32(r + 20);
     const bool rev = (fqb_ld16(r + 18) & 0x10u) != 0;
     for (; b < uend; ++b) {
-      const uint8_t c = fq_bam_text_byte(r, nm, l, n_cig, rev, (uint32_t)(b - a.off[e][u]));
+      const uint8_t c = fq_bam_text_byte(r, nm, l, n_cig, rev, (uint32_t)(b - a.off[e][u]), oq);
       if (whole) { const uint32_t k = (uint32_t)(b - (uint64_t)lo_b); w[k >> 2] |= (uint32_t)c << (8 * (k & 3)); } else a.text[e][b] = c;
     }
   }
@@ -247,6 +345,7 @@ FQ_HD uint64_t fq_bam_fill_pieces(const FqBamFillArgs &a, int e) { return a.tota
 // ---- (b') collation ----
 FQ_HD const uint8_t *fqc_rec(const FqBamCollateArgs &a, uint32_t c) { return c < a.n_held ? a.held + a.hoff[c] : a.pay + a.starts[a.kidx[c - a.n_held]]; }
 FQ_HD uint64_t fqc_ord(const FqBamCollateArgs &a, uint32_t c) { return c < a.n_held ? a.hord[c] : a.ord0 + a.kidx[c - a.n_held]; }
+FQ_HD uint32_t fqc_oq(const FqBamCollateArgs &a, uint32_t c) { return c < a.n_held ? a.hoq[c] : a.roq[a.kidx[c - a.n_held]]; }      // (where a.roq is given)
 // 64 bits of l_read_name and the name's bytes (FNV-1a, then a finaliser so that any k low bits group evenly).  The hash only groups: equality is
 // always l_read_name and a byte compare (fqc_same_name).
 FQ_HD uint64_t fqc_hash(const uint8_t *r) {
@@ -311,6 +410,7 @@ FQ_HD void fq_bam_cunit_thread(const FqBamCollateArgs &a, uint32_t k) {
     a.from[e][u] = x < a.n_held ? 1 : 0;
     a.src[e][u] = x < a.n_held ? x : a.starts[a.kidx[x - a.n_held]];
     a.len[e][u] = fq_bam_text_len(fqc_rec(a, x));
+    if (a.roq) a.oq[e][u] = fqc_oq(a, x);
   }
 }
 // what stays: candidate c still waits -- its bytes (block_size included) -- or does not
@@ -324,7 +424,7 @@ FQ_HD void fq_bam_chold_lane(const FqBamCollateArgs &a, uint32_t c, uint32_t lan
   const uint8_t *s = fqc_rec(a, c);
   const uint64_t d0 = a.soff[c], len = a.rlen[c];
   for (uint64_t k = lane; k < len; k += 64) a.nheld[d0 + k] = s[k];
-  if (lane == 0) { const uint64_t j = a.sidx[c]; a.noff[j] = d0; a.nkey[j] = a.hash[c]; a.nord[j] = fqc_ord(a, c); }
+  if (lane == 0) { const uint64_t j = a.sidx[c]; a.noff[j] = d0; a.nkey[j] = a.hash[c]; a.nord[j] = fqc_ord(a, c); if (a.roq) a.noq[j] = fqc_oq(a, c); }
 }
 FQ_HD uint64_t fqc_mask(int bits) { return bits <= 0 ? 0ull : bits >= 64 ? ~0ull : (1ull << bits) - 1ull; }
 #define FQC_HASH_BITS 32      // the bits of the hash that group by default: four passes of the sort; the records of equal hashes meet in one run, and there a byte compare decides
@@ -336,6 +436,7 @@ int launch_bam_rewalk(const FqBamChainArgs &a, uint32_t k, uint32_t p, int to_en
 int launch_bam_starts(const FqBamChainArgs &a);                                 // a thread per member
 int launch_bam_keep(const FqBamPairArgs &a);                                    // a thread per record
 int launch_bam_kidx(const FqBamPairArgs &a);
+int launch_bam_tags(const FqBamTagArgs &a);                                     // a thread per record; *a.bad lowered to the first refusal of kinds 8 / 9
 int launch_bam_units(const FqBamPairArgs &a);                                   // a thread per pair; *a.bad lowered to the first refusal
 int launch_bam_fill(const FqBamFillArgs &a);                                    // a wavefront per (pair, side) (FASTQUICK_BAM_FILL=pieces: a thread per sixteen destination bytes, A/B)
 int bam_hash_bits();                                                            // FASTQUICK_BAM_HASH_BITS=k (0..64; tests: many names in one run), or FQC_HASH_BITS
@@ -357,6 +458,7 @@ inline int launch_bam_rewalk(const FqBamChainArgs &a, uint32_t k, uint32_t p, in
 inline int launch_bam_starts(const FqBamChainArgs &a) { for (uint32_t k = 0; k < a.n_seg; ++k) fq_bam_starts_thread(a, k); return 0; }
 inline int launch_bam_keep(const FqBamPairArgs &a) { for (uint32_t i = 0; i < a.n_rec; ++i) fq_bam_keep_thread(a, i); return 0; }
 inline int launch_bam_kidx(const FqBamPairArgs &a) { for (uint32_t i = 0; i < a.n_rec; ++i) fq_bam_kidx_thread(a, i); return 0; }
+inline int launch_bam_tags(const FqBamTagArgs &a) { for (uint32_t i = 0; i < a.n_rec; ++i) *a.bad = fqb_min64(*a.bad, fq_bam_tags_thread(a, i)); return 0; }
 inline int launch_bam_units(const FqBamPairArgs &a) { for (uint32_t u = 0; u < a.n_units; ++u) *a.bad = fqb_min64(*a.bad, fq_bam_unit_thread(a, u)); return 0; }
 inline int launch_bam_fill(const FqBamFillArgs &a) {      // (the variable is read at every call here, so that one test process holds either body to the texts)
   const char *form = getenv("FASTQUICK_BAM_FILL");

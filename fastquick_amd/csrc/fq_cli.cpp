@@ -106,6 +106,8 @@ struct Args {
   long long collate_mem = 4ll << 30;   // --collate_mem: bytes the records waiting for their mates may take in device memory
   bool collate_mem_given = false;
   std::string bam_in;         // --bam_in: one BAM file in place of the FASTQ files (fq_frontend_open_bam: its records are transcoded to FASTQ text on the device)
+  std::vector<std::string> bam_rg;   // --bam_rg ID (repeatable): only the records of --bam_in whose RG:Z is one of these are read (fq_frontend_open_bam_select)
+  bool bam_oq = false;        // --bam_oq: a record that has OQ:Z gives that as its quality line (the sequencer's qualities of a recalibrated file)
   int bam_l_seq = 0;          // ... the first kept record's length (fq_bam_probe): sizes the rows as a FASTQ file's first record does
   std::string fq_list, rg = "@RG\\tID:foo\\tSM:bar";   // runAlign's default --RG (src/FASTQuick.cpp:170)
   bool cal_dup = true;
@@ -114,7 +116,7 @@ struct Args {
 };
 
 int usage() {
-  fprintf(stderr, "Usage: FASTQuick_amd align --index_prefix P --fastq_1 R1.fq[.gz] [--fastq_2 R2.fq[.gz]] | --fq_list LIST | --bam_in X.bam [--collate [--collate_mem BYTES]]  --out_prefix O [--sam_out | --sorted_bam [--sort_mem BYTES]] [--bam_deflate fixed|dynamic] [--RG STR] [--cal_dup]\n"
+  fprintf(stderr, "Usage: FASTQuick_amd align --index_prefix P --fastq_1 R1.fq[.gz] [--fastq_2 R2.fq[.gz]] | --fq_list LIST | --bam_in X.bam [--collate [--collate_mem BYTES]] [--bam_rg ID]... [--bam_oq]  --out_prefix O [--sam_out | --sorted_bam [--sort_mem BYTES]] [--bam_deflate fixed|dynamic] [--RG STR] [--cal_dup]\n"
                   "                       [--q INT] [--n FLOAT|INT] [--kmer_thresh INT] [--o INT] [--e INT] [--i INT] [--d INT] [--l INT] [--k INT]\n"
                   "                       [--m INT] [--R INT] [--N] [--L] [--I] [--max_isize INT] [--max_occ INT] [--is_sw] [--n_multi INT] [--N_multi INT]\n"
                   "                       [--ap_prior FLOAT] [--force_isize] [--frac_samp FLOAT] [--t INT] [--chunk_pairs INT] [--batch_pairs INT] [--device INT | --devices LIST] [--read_len INT] [--clean_names] [--strict_reference] [--host_reader] [--host_consumers]\n"
@@ -355,8 +357,14 @@ fq_frontend_t *open_device_front_end(const Args &A, const std::string &f1, const
   if (A.host_reader || A.frac < 1.0) return nullptr;       // (--frac_samp: the reference's generator is walked record by record, on the host)
   fq_frontend_t *fe = nullptr;
   if (!A.bam_in.empty()) {
-    const int rc = A.collate ? fq_frontend_open_bam_collate(device, A.bam_in.c_str(), A.o.batch_pairs, A.chunk_pairs, slot_mode, stride, A.collate_mem, &fe)
-                             : fq_frontend_open_bam(device, A.bam_in.c_str(), A.o.batch_pairs, A.chunk_pairs, slot_mode, stride, &fe);
+    std::vector<const char *> ids;
+    for (const std::string &id : A.bam_rg) ids.push_back(id.c_str());
+    const fq_bam_select_t sel{ids.data(), (int32_t)ids.size(), A.bam_oq ? 1 : 0};
+    const bool tags = !ids.empty() || A.bam_oq;      // (neither option: the entries as they were, kernel for kernel)
+    const int rc = A.collate ? (tags ? fq_frontend_open_bam_collate_select(device, A.bam_in.c_str(), A.o.batch_pairs, A.chunk_pairs, slot_mode, stride, A.collate_mem, &sel, &fe)
+                                     : fq_frontend_open_bam_collate(device, A.bam_in.c_str(), A.o.batch_pairs, A.chunk_pairs, slot_mode, stride, A.collate_mem, &fe))
+                             : (tags ? fq_frontend_open_bam_select(device, A.bam_in.c_str(), A.o.batch_pairs, A.chunk_pairs, slot_mode, stride, &sel, &fe)
+                                     : fq_frontend_open_bam(device, A.bam_in.c_str(), A.o.batch_pairs, A.chunk_pairs, slot_mode, stride, &fe));
     mark("front end open");
     if (rc) die("--bam_in: cannot start the front end on device " + std::to_string(device) + " for " + A.bam_in + " (" + std::to_string(rc) + ")");
     return fe;
@@ -367,7 +375,7 @@ fq_frontend_t *open_device_front_end(const Args &A, const std::string &f1, const
   if (rc) die("cannot start the front end on device " + std::to_string(device) + " (" + std::to_string(rc) + ")");
   return fe;
 }
-void front_end_notice(fq_frontend_t *fe) {
+void front_end_notice(fq_frontend_t *fe, bool bam_tags = false) {
   fq_frontend_stats_t st;
   fq_frontend_stats(fe, &st);
   fprintf(stderr, "NOTICE - front end on the device: %lld pairs, %lld BGZF members (%lld left to the host's decoder), %.1f MB -> %.1f MB of text; inflate %.1f ms ; lines, records, keys, slots %.1f ms\n",
@@ -375,6 +383,9 @@ void front_end_notice(fq_frontend_t *fe) {
   if (st.bam_records || st.ms_transcode > 0)
     fprintf(stderr, "NOTICE - BAM input on the device: %lld records (%lld skipped as secondary or supplementary), %lld repairs of the record chain; records -> text %.1f ms (starts %.1f, pairs %.1f, fill %.1f)\n",
             (long long)st.bam_records, (long long)st.bam_skipped, (long long)st.chain_repairs, st.ms_transcode, st.ms_bam_starts, st.ms_bam_pairs, st.ms_bam_fill);
+  if (bam_tags)
+    fprintf(stderr, "NOTICE - BAM input, auxiliary fields walked on the device: %lld records of other read groups left out, %lld records with their quality line from OQ; tag kernel %.1f ms\n",
+            (long long)st.bam_unselected, (long long)st.bam_oq_records, st.ms_bam_tags);
   if (st.ms_bam_collate > 0 || st.bam_held_peak_records)
     fprintf(stderr, "NOTICE - BAM input collated on the device: at most %lld records (%.1f MB) waited for their mates; collation kernels %.1f ms\n",
             (long long)st.bam_held_peak_records, 1e-6 * (double)st.bam_held_peak_bytes, st.ms_bam_collate);
@@ -513,7 +524,7 @@ struct Stream {
     finish_prev();
     if (other) ctx = other;             // the context that holds the stream's state (the host readers' part, if any, goes on with it)
     unequal_on_device = fq_frontend_unequal_lengths(fe) != 0;
-    front_end_notice(fe);
+    front_end_notice(fe, !A.bam_rg.empty() || A.bam_oq);
   }
 
   // ---- the host readers' part (all of it for files that are not BGZF): the next chunk is read and tokenised while the device aligns the
@@ -771,7 +782,25 @@ bool probe_bam_input(Args &A) {
   if (A.frac < 1.0) die("--bam_in cannot be combined with --frac_samp below 1 (sampling walks the records on the host)");
   if (!A.devices.empty() && parse_devices(A.devices).size() > 1) die("--bam_in cannot be combined with --devices naming more than one device (sharding takes host readers)");
   fq_bam_probe_t pr;
-  if (fq_bam_probe(A.bam_in.c_str(), &pr)) die(std::string("--bam_in: ") + pr.error);
+  if (!A.bam_rg.empty()) {                       // every wanted ID is one of the header's @RG lines: said before any device work
+    int32_t n = 0;
+    int64_t nb = 0;
+    int rc = fq_bam_read_groups(A.bam_in.c_str(), nullptr, 0, &n, &nb);
+    std::vector<char> buf((size_t)nb + 1);
+    if (rc == FQ_ELIMIT) rc = fq_bam_read_groups(A.bam_in.c_str(), buf.data(), nb, &n, &nb);
+    if (rc) { if (fq_bam_probe(A.bam_in.c_str(), &pr)) die(std::string("--bam_in: ") + pr.error); die("--bam_in: the header's @RG lines cannot be read"); }
+    std::vector<std::string> have;
+    for (const char *q = buf.data(); (int32_t)have.size() < n; q += have.back().size() + 1) have.emplace_back(q);
+    std::string list;
+    for (const std::string &h : have) list += (list.empty() ? "" : ", ") + h;
+    for (const std::string &id : A.bam_rg)
+      if (std::find(have.begin(), have.end(), id) == have.end())
+        die("--bam_rg " + id + ": " + A.bam_in + " has no @RG line with this ID; its header holds " + (have.empty() ? std::string("no @RG line") : std::to_string(have.size()) + ": " + list));
+  }
+  std::vector<const char *> ids;
+  for (const std::string &id : A.bam_rg) ids.push_back(id.c_str());
+  const fq_bam_select_t sel{ids.data(), (int32_t)ids.size(), A.bam_oq ? 1 : 0};
+  if (ids.empty() ? fq_bam_probe(A.bam_in.c_str(), &pr) : fq_bam_probe_select(A.bam_in.c_str(), &sel, &pr)) die(std::string("--bam_in: ") + pr.error);
   A.bam_l_seq = pr.first_l_seq;
   if (!strcmp(pr.sort_order, "coordinate") && !A.collate) fprintf(stderr, "NOTICE - %s says SO:coordinate: mates must be adjacent (collate the file by name first)\n", A.bam_in.c_str());
   return pr.paired != 0;
@@ -1071,6 +1100,8 @@ int main(int argc, char **argv) {
     else if (f == "--frac_samp") A.frac = atof(need(""));
     else if (f == "--bam_in") A.bam_in = need("");
     else if (f == "--collate") A.collate = true;
+    else if (f == "--bam_rg") A.bam_rg.push_back(need(""));
+    else if (f == "--bam_oq") A.bam_oq = true;
     else if (f == "--collate_mem") { A.collate_mem = atoll(need("")); A.collate_mem_given = true; if (A.collate_mem < 0) die("--collate_mem must not be negative"); }
     else die("unknown option " + f);
   }
@@ -1083,6 +1114,8 @@ int main(int argc, char **argv) {
   if (A.sorted_bam && A.sam_out) die("--sorted_bam writes a BAM file: it cannot be combined with --sam_out (sorting the SAM text is not supported)");
   if (A.bam_deflate >= 0 && A.sam_out) die("--bam_deflate chooses how the BAM file is compressed: it cannot be combined with --sam_out");
   if (A.collate && A.bam_in.empty()) die("--collate finds the mates of a BAM file: it needs --bam_in");
+  if (!A.bam_rg.empty() && A.bam_in.empty()) die("--bam_rg selects read groups of a BAM file: it needs --bam_in (--RG names the output's group)");
+  if (A.bam_oq && A.bam_in.empty()) die("--bam_oq reads the OQ qualities of a BAM file: it needs --bam_in");
   if (A.collate_mem_given && !A.collate) die("--collate_mem bounds what --collate holds: it needs --collate");
   if (A.out_prefix == "Empty") die("--out_prefix is required");
   if (A.index_prefix == "Empty") die("--index_prefix is required");

@@ -1899,6 +1899,11 @@ __global__ void __launch_bounds__(256) k_bam_units(FqBamPairArgs a) {
   const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
   bam_commit_bad(u < a.n_units ? fq_bam_unit_thread(a, u) : FQB_NO_BAD, a.bad);
 }
+// (b''; --bam_rg / --bam_oq) a thread per record walks its auxiliary fields: 100-250 bytes, serial by format, a record a lane
+__global__ void __launch_bounds__(256) k_bam_tags(FqBamTagArgs a) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  bam_commit_bad(i < a.n_rec ? fq_bam_tags_thread(a, i) : FQB_NO_BAD, a.bad);
+}
 __global__ void __launch_bounds__(256) k_bam_fill(FqBamFillArgs a) {
   const uint64_t w = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
   const uint32_t u = (uint32_t)(w / (uint32_t)a.n_sides);
@@ -1936,6 +1941,13 @@ int launch_bam_kidx(const FqBamPairArgs &a) {
   FQ_PRE();
   if (!a.n_rec) return 0;
   hipLaunchKernelGGL(k_bam_kidx, dim3(nblk(a.n_rec, 256)), dim3(256), 0, g_stream, a);
+  FQ_HIP(hipGetLastError());
+  return 0;
+}
+int launch_bam_tags(const FqBamTagArgs &a) {
+  FQ_PRE();
+  if (!a.n_rec) return 0;
+  hipLaunchKernelGGL(k_bam_tags, dim3(nblk(a.n_rec, 256)), dim3(256), 0, g_stream, a);
   FQ_HIP(hipGetLastError());
   return 0;
 }

@@ -255,10 +255,34 @@ inline double ms_since(std::chrono::steady_clock::time_point t0) { return std::c
 
 namespace {
 // ---- BAM input (fq_bamin.h): the scratch of the transcoding kernels, and what a stream keeps from chunk to chunk ----
+// the wanted IDs as fq_bamin.h's tag body reads them, on the device and in the probe: dwords -- their count, their lengths, then their bytes
+void pack_bam_ids(const fq_bam_select_t *sl, std::vector<uint32_t> *out) {
+  out->clear();
+  const int32_t n = sl && sl->ids ? std::max<int32_t>(sl->n_ids, 0) : 0;
+  if (!n) return;
+  std::string bytes;
+  out->push_back((uint32_t)n);
+  for (int32_t k = 0; k < n; ++k) { const std::string id = sl->ids[k] ? sl->ids[k] : ""; out->push_back((uint32_t)id.size()); bytes += id; }
+  bytes.resize((bytes.size() + 4) & ~(size_t)3);
+  const size_t at = out->size();
+  out->resize(at + bytes.size() / 4);
+  memcpy(out->data() + at, bytes.data(), bytes.size());
+}
 struct BamWork {
   DBuf<uint32_t> seg, res, starts, kept, kidx, len[2], src[2];
   DBuf<uint64_t> base, kord, off[2], bad;
   std::vector<uint32_t> h_seg, h_res;
+  // --bam_rg / --bam_oq (fq_bamin.h (b'')): the wanted IDs as the tag kernel reads them, and what it writes per record; per unit and side the OQ offsets
+  bool tags = false, sel_up = false;
+  int use_oq = 0;
+  std::vector<uint32_t> h_sel;
+  DBuf<uint32_t> sel, roq, unsel, hasoq, oq[2];
+  DBuf<uint64_t> uord, qord;
+  void select(const fq_bam_select_t *sl) {       // (before the first chunk)
+    pack_bam_ids(sl, &h_sel);
+    sel_up = false; use_oq = sl && sl->use_oq ? 1 : 0;
+    tags = !h_sel.empty() || use_oq;
+  }
 };
 struct BamChunk {                              // what the kernels found in one chunk's payload
   uint32_t n_rec = 0, n_kept = 0, n_units = 0;
@@ -267,6 +291,8 @@ struct BamChunk {                              // what the kernels found in one 
   uint32_t used_rec = 0;                       // records in front of carry_from
   int end_flag = FQB_SEG_OK, repairs = 0, paired = 0;
   uint64_t bad = FQB_NO_BAD, text_len[2] = {0, 0};
+  uint64_t tag_bad = FQB_NO_BAD;               // (--bam_rg / --bam_oq) the tag kernel's first refusal, over all records of the payload
+  uint32_t n_unsel = 0, n_oq = 0;              // ... of the records in front of carry_from: not selected; kept with an OQ value
 };
 // --collate: the records that wait for their mates, in HBM from chunk to chunk (two halves: a chunk's survivors are gathered from one into the other),
 // with their offsets, name hashes and ordinals; and the scratch of the collation kernels
@@ -275,6 +301,7 @@ struct BamHeld {
   uint64_t mem = 0;                            // collate_mem: the most a half may hold (records + 24 bytes of arrays a record)
   DBuf<uint8_t> rec[2];
   DBuf<uint64_t> off[2], key[2], ord[2];
+  DBuf<uint32_t> oq[2];                        // (--bam_oq) the held records' OQ offsets: 4 bytes more a record
   int cur = 0;
   uint32_t n = 0;                              // records held now
   uint64_t bytes = 0;
@@ -295,8 +322,8 @@ struct BamState {
   DBuf<uint8_t> d_pay[2];                      // the chunks' payloads in turn: the raw carry of one leads the next
   int cur = 0;
   uint64_t carry_from = 0, carry_len = 0, ord0 = 0;
-  int64_t records = 0, skipped = 0, repairs = 0;
-  double ms_starts = 0, ms_pairs = 0, ms_fill = 0;
+  int64_t records = 0, skipped = 0, repairs = 0, unselected = 0, oq_records = 0, empty_chunks = 0;
+  double ms_starts = 0, ms_pairs = 0, ms_fill = 0, ms_tags = 0;
   double pay_total = 0, text0_total = 0;
 };
 }  // namespace
@@ -509,9 +536,9 @@ int host_inflate_refused(CompChunk &C, uint8_t *text, const std::string &path, i
 
 // ---- BAM input: records of a payload in HBM -> the two FASTQ texts (kernels: fq_bamin.h) ------------------------------------------------
 std::string bam_bad_message(uint64_t bad) {
-  const unsigned long long ord = (unsigned long long)(bad >> 3);
+  const unsigned long long ord = (unsigned long long)fqb_bad_ord(bad);
   const char *what = "is refused";
-  switch ((int)(bad & 7)) {
+  switch ((int)fqb_bad_kind(bad)) {
     case FQB_BAD_MIXED: what = "paired and single-end records are mixed in one stream"; break;
     case FQB_BAD_LSEQ0: what = "a record without bases (l_seq == 0)"; break;
     case FQB_BAD_FIELDS: what = "the record's fields do not fit its block_size"; break;
@@ -519,6 +546,8 @@ std::string bam_bad_message(uint64_t bad) {
     case FQB_BAD_MATES: what = "mates are not adjacent: collate the file by name first (the two records are not a first and a second mate)"; break;
     case FQB_BAD_NAMES: what = "mates are not adjacent: collate the file by name first (the two records' names differ)"; break;
     case FQB_BAD_DUP: what = "a second record of this name and side before the mate of the first"; break;
+    case FQB_BAD_AUX: what = "auxiliary fields cannot be walked (an unknown type, a value beyond the record, a Z / H value without NUL, stray bytes, or an RG / OQ tag that is not of type Z)"; break;
+    case FQB_BAD_OQ: what = "OQ does not fit the read (its length is not l_seq, or a byte lies outside 0x21..0x7e)"; break;
   }
   return "BAM record " + std::to_string(ord) + ": " + what;
 }
@@ -576,15 +605,44 @@ int bam_chain_kept(BamWork &W, const uint8_t *d_pay, uint32_t n, uint32_t rec0, 
   FQB_TRY(fqdev::launch_bam_starts(a));
   fqdev::time_end(4);
   // ---- (b) kept records, pairs, lengths
+  if (W.tags) {                                  // (b''; its buffers and the IDs first: an allocation inside a timed region counts as that region's)
+    const size_t nr = (size_t)R->n_rec;
+    if (!W.roq.ensure(nr + 1) || !W.unsel.ensure(nr + 1) || !W.hasoq.ensure(nr + 1) || !W.uord.ensure(nr + 2) || !W.qord.ensure(nr + 2) || (!W.h_sel.empty() && !W.sel.ensure(W.h_sel.size()))) { *err = "out of device memory (BAM records)"; return FQ_ENOMEM; }
+    if (!W.h_sel.empty() && !W.sel_up) { FQB_TRY(fqdev::h2d(W.sel.p, W.h_sel.data(), 4 * W.h_sel.size()) || fqdev::sync()); W.sel_up = true; }
+  }
   fqdev::time_begin(5);
   FqBamPairArgs &b = *pb;
   b = FqBamPairArgs();
   b.pay = d_pay; b.starts = W.starts.p; b.n_rec = R->n_rec; b.kept = W.kept.p; b.kord = W.kord.p; b.kidx = W.kidx.p; b.ord0 = ord0; b.bad = W.bad.p;
   uint64_t n_kept = 0;
-  FQB_TRY(fqdev::launch_bam_keep(b) || fqdev::launch_scan(W.kept.p, W.kord.p, R->n_rec) || fqdev::d2h(&n_kept, W.kord.p + R->n_rec, 8) || fqdev::sync());
+  if (W.tags) {                                  // (b''): who is kept says the walk of the auxiliary fields (timing id 12)
+    FqBamTagArgs t{};
+    t.pay = d_pay; t.starts = W.starts.p; t.n_rec = R->n_rec; t.ord0 = ord0; t.sel = W.h_sel.empty() ? nullptr : W.sel.p; t.use_oq = W.use_oq;
+    t.kept = W.kept.p; t.roq = W.roq.p; t.unsel = W.unsel.p; t.hasoq = W.hasoq.p; t.bad = W.bad.p + 1;
+    const uint64_t no_bad = FQB_NO_BAD;
+    FQB_TRY(fqdev::h2d(W.bad.p + 1, &no_bad, 8));
+    fqdev::time_begin(12);
+    FQB_TRY(fqdev::launch_bam_tags(t));
+    fqdev::time_end(12);
+    FQB_TRY(fqdev::launch_scan(W.unsel.p, W.uord.p, R->n_rec) || fqdev::launch_scan(W.hasoq.p, W.qord.p, R->n_rec) || fqdev::d2h(&R->tag_bad, W.bad.p + 1, 8));
+    if (W.use_oq) b.roq = W.roq.p;
+  } else {
+    FQB_TRY(fqdev::launch_bam_keep(b));
+  }
+  FQB_TRY(fqdev::launch_scan(W.kept.p, W.kord.p, R->n_rec) || fqdev::d2h(&n_kept, W.kord.p + R->n_rec, 8) || fqdev::sync());
   FQB_TRY(fqdev::launch_bam_kidx(b));
   R->n_kept = (uint32_t)n_kept;
   fqdev::time_end(5);
+  return FQ_OK;
+}
+// (b'') behind the pairing: the counts over the records in front of carry_from, and the tag kernel's first refusal where its record lies there (a carried
+// record is walked again with the next chunk, and what its unit may refuse it for comes first)
+int bam_tag_results(BamWork &W, uint64_t ord0, BamChunk *R, std::string *err) {
+  if (!W.tags || !R->n_rec) return FQ_OK;
+  uint64_t u = 0, q = 0;
+  FQB_TRY(fqdev::d2h(&u, W.uord.p + R->used_rec, 8) || fqdev::d2h(&q, W.qord.p + R->used_rec, 8) || fqdev::sync());
+  R->n_unsel = (uint32_t)u; R->n_oq = (uint32_t)q;
+  if (R->tag_bad != FQB_NO_BAD && fqb_bad_ord(R->tag_bad) < ord0 + R->used_rec) R->bad = std::min(R->bad, R->tag_bad);
   return FQ_OK;
 }
 // Kernels (a) and (b) over pay[0, n): the chain of records from rec0, cut at `cuts` (the members' starts behind rec0); who is kept, who pairs with
@@ -616,21 +674,22 @@ int bam_records(BamWork &W, const uint8_t *d_pay, uint32_t n, uint32_t rec0, con
   }
   const uint32_t U = R->n_units;
   const int sides = R->paired ? 2 : 1;
-  for (int e = 0; e < sides; ++e) if (!W.src[e].ensure(U + 1) || !W.len[e].ensure(U + 1) || !W.off[e].ensure(U + 2)) { *err = "out of device memory (BAM records)"; return FQ_ENOMEM; }
+  for (int e = 0; e < sides; ++e) if (!W.src[e].ensure(U + 1) || !W.len[e].ensure(U + 1) || !W.off[e].ensure(U + 2) || (b.roq && !W.oq[e].ensure(U + 1))) { *err = "out of device memory (BAM records)"; return FQ_ENOMEM; }
   b.n_units = U; b.paired = R->paired;
-  for (int e = 0; e < 2; ++e) { b.src[e] = W.src[e].p; b.len[e] = W.len[e].p; }
+  for (int e = 0; e < 2; ++e) { b.src[e] = W.src[e].p; b.len[e] = W.len[e].p; b.oq[e] = W.oq[e].p; }
   const uint64_t no_bad = FQB_NO_BAD;
   FQB_TRY(fqdev::h2d(W.bad.p, &no_bad, 8) || fqdev::launch_bam_units(b));
   for (int e = 0; e < sides; ++e) FQB_TRY(fqdev::launch_scan(W.len[e].p, W.off[e].p, U) || fqdev::d2h(&R->text_len[e], W.off[e].p + U, 8));
   FQB_TRY(fqdev::d2h(&R->bad, W.bad.p, 8) || fqdev::sync());
   fqdev::time_end(5);
-  return FQ_OK;
+  return bam_tag_results(W, ord0, R, err);
 }
 // Kernel (c): the texts of the chunk's units at text[e] (timing id 6)
 int bam_fill(BamWork &W, const uint8_t *d_pay, const BamChunk &R, uint8_t *const text[2], std::string *err, const BamHeld *K = nullptr) {
   FqBamFillArgs f{};
   f.pay = d_pay; f.n_units = R.n_units; f.n_sides = R.paired ? 2 : 1;
   for (int e = 0; e < f.n_sides; ++e) { f.src[e] = W.src[e].p; f.off[e] = W.off[e].p; f.text[e] = text[e]; f.total[e] = R.text_len[e]; }
+  if (W.tags && W.use_oq) { f.oq[0] = W.oq[0].p; f.oq[1] = W.oq[1].p; }      // (--bam_oq: where a side's record has an OQ value, its quality line is that)
   if (K) { f.held = K->rec[K->cur].p; f.hoff = K->off[K->cur].p; f.from[0] = K->from[0].p; f.from[1] = K->from[1].p; }      // (collation: a side's record lies in the payload or in the held store)
   fqdev::time_begin(6);
   FQB_TRY(fqdev::launch_bam_fill(f));
@@ -648,6 +707,7 @@ FqBamCollateArgs collate_args(BamWork &W, BamHeld &K, const uint8_t *d_pay, uint
   for (int e = 0; e < 2; ++e) { c.from[e] = K.from[e].p; c.src[e] = W.src[e].p; c.len[e] = W.len[e].p; }
   c.bad = W.bad.p; c.surv = K.surv.p; c.rlen = K.rlen.p; c.sidx = K.sidx.p; c.soff = K.soff.p;
   c.nheld = K.rec[K.cur ^ 1].p; c.noff = K.off[K.cur ^ 1].p; c.nkey = K.key[K.cur ^ 1].p; c.nord = K.ord[K.cur ^ 1].p;
+  if (W.tags && W.use_oq) { c.roq = W.roq.p; c.hoq = K.oq[K.cur].p; c.noq = K.oq[K.cur ^ 1].p; c.oq[0] = W.oq[0].p; c.oq[1] = W.oq[1].p; }
   return c;
 }
 // The collating sibling of bam_records, for a paired stream: kernel (a) and who is kept as there; then the candidates -- the held records, then the
@@ -662,7 +722,7 @@ int bam_collate_records(BamWork &W, BamHeld &K, const uint8_t *d_pay, uint32_t n
   FqBamPairArgs b{};
   if (const int rc = bam_chain_kept(W, d_pay, n, rec0, cuts, n_ref, ord0, R, &b, err)) return rc;
   K.n_kept = R->n_kept;
-  if (!K.n_kept) return FQ_OK;                   // (no candidate of this chunk: what is held stays as it is)
+  if (!K.n_kept) return bam_tag_results(W, ord0, R, err);      // (no candidate of this chunk: what is held stays as it is)
   const uint64_t N64 = (uint64_t)K.n + K.n_kept;
   if (N64 > 0x7fffffffull) { *err = "more than 2^31 BAM records waiting for their mates"; return FQ_ELIMIT; }
   const uint32_t N = (uint32_t)N64, tiles = fq_sort_tiles(N);
@@ -685,13 +745,13 @@ int bam_collate_records(BamWork &W, BamHeld &K, const uint8_t *d_pay, uint32_t n
   uint64_t n_units = 0;
   FQB_TRY(fqdev::launch_scan(K.flag.p, K.uidx.p, K.n_kept) || fqdev::d2h(&n_units, K.uidx.p + K.n_kept, 8) || fqdev::sync());
   const uint32_t U = R->n_units = (uint32_t)n_units;
-  for (int e = 0; e < 2; ++e) if (!W.src[e].ensure(U + 1) || !W.len[e].ensure(U + 1) || !W.off[e].ensure(U + 2) || !K.from[e].ensure(U + 1)) { *err = "out of device memory (BAM collation)"; return FQ_ENOMEM; }
+  for (int e = 0; e < 2; ++e) if (!W.src[e].ensure(U + 1) || !W.len[e].ensure(U + 1) || !W.off[e].ensure(U + 2) || !K.from[e].ensure(U + 1) || (W.tags && W.use_oq && !W.oq[e].ensure(U + 1))) { *err = "out of device memory (BAM collation)"; return FQ_ENOMEM; }
   c = collate_args(W, K, d_pay, ord0);
   FQB_TRY(fqdev::launch_bam_cunits(c));
   for (int e = 0; e < 2; ++e) FQB_TRY(fqdev::launch_scan(W.len[e].p, W.off[e].p, U) || fqdev::d2h(&R->text_len[e], W.off[e].p + U, 8));
   FQB_TRY(fqdev::d2h(&R->bad, W.bad.p, 8) || fqdev::sync());
   fqdev::time_end(10);
-  return FQ_OK;
+  return bam_tag_results(W, ord0, R, err);
 }
 // Behind the chunk's fill: the candidates that still wait -- old held records and new ones, in ordinal order -- are gathered into the other half of the
 // held store, a wavefront a record.  FQ_ELIMIT where they would take more than collate_mem.  Timing id 11.
@@ -703,14 +763,15 @@ int bam_collate_hold(BamWork &W, BamHeld &K, const uint8_t *d_pay, uint64_t ord0
   fqdev::time_begin(11);
   FQB_TRY(fqdev::launch_bam_cmark(c) || fqdev::launch_scan(K.surv.p, K.sidx.p, N) || fqdev::launch_scan(K.rlen.p, K.soff.p, N) || fqdev::d2h(&count, K.sidx.p + N, 8) || fqdev::d2h(&bytes, K.soff.p + N, 8) ||
           fqdev::sync());
-  const uint64_t total = bytes + 24 * count;
+  const bool with_oq = W.tags && W.use_oq;
+  const uint64_t total = bytes + (with_oq ? 28 : 24) * count;
   if (total > K.mem) {
     *err = "BAM record " + std::to_string(ord0) + ": behind the chunk that begins here " + std::to_string(count) + " records wait for their mates, " + std::to_string(total) +
            " bytes: more than --collate_mem " + std::to_string(K.mem) + " (a file with many mates far apart, or many records without a mate)";
     return FQ_ELIMIT;
   }
   const int o = K.cur ^ 1;
-  if (!K.rec[o].ensure((size_t)bytes + 1) || !K.off[o].ensure(count + 1) || !K.key[o].ensure(count + 1) || !K.ord[o].ensure(count + 1)) { *err = "out of device memory (BAM records waiting for their mates)"; return FQ_ENOMEM; }
+  if (!K.rec[o].ensure((size_t)bytes + 1) || !K.off[o].ensure(count + 1) || !K.key[o].ensure(count + 1) || !K.ord[o].ensure(count + 1) || (with_oq && !K.oq[o].ensure(count + 1))) { *err = "out of device memory (BAM records waiting for their mates)"; return FQ_ENOMEM; }
   c = collate_args(W, K, d_pay, ord0);
   FQB_TRY(fqdev::launch_bam_chold(c) || fqdev::sync());
   fqdev::time_end(11);
@@ -780,10 +841,17 @@ int bam_chunk(fq_frontend *fe, CompChunk &C, int slot, Ahead &next, std::string 
   if (collate) {
     if (const int rc = bam_collate_hold(S.W, S.K, buf.p, S.ord0, err)) { *err = F0.path + ": " + *err; return rc; }
     if (C.eof) S.K.orphans = S.K.n;               // what still waits at the end of the stream has no mate in it
+    if (C.eof && S.K.n && S.W.tags && S.W.use_oq) {      // (... and its OQ values were read by nobody)
+      std::vector<uint32_t> hoq(S.K.n);
+      FQB_TRY(fqdev::d2h(hoq.data(), S.K.oq[S.K.cur].p, 4 * (size_t)S.K.n) || fqdev::sync());
+      for (uint32_t v : hoq) if (v) --S.oq_records;
+    }
   }
   // what the stream keeps
   S.cur ^= 1; S.carry_from = R.carry_from; S.carry_len = n - R.carry_from;
-  S.ord0 += R.used_rec; S.records += R.used_rec; S.skipped += collate ? (int64_t)R.n_rec - (int64_t)R.n_kept : (int64_t)R.used_rec - (int64_t)R.n_units * (R.paired ? 2 : 1); S.repairs += R.repairs;
+  S.ord0 += R.used_rec; S.records += R.used_rec; S.skipped += (collate ? (int64_t)R.n_rec - (int64_t)R.n_kept : (int64_t)R.used_rec - (int64_t)R.n_units * (R.paired ? 2 : 1)) - (int64_t)R.n_unsel; S.repairs += R.repairs;
+  S.unselected += R.n_unsel; S.oq_records += R.n_oq;
+  if (R.n_rec && !R.n_kept) ++S.empty_chunks;
   S.pay_total += (double)(R.carry_from - rec0); S.text0_total += (double)R.text_len[0];
   fe->n_members += (int64_t)C.mem.size(); fe->n_refused += refused; fe->comp_bytes += (int64_t)C.comp_len; fe->text_bytes += (int64_t)(R.text_len[0] + R.text_len[1]);
   // (under collation a chunk's text says nothing about its payload -- it may complete no pair at all: the open's estimate of the scale stands)
@@ -1097,7 +1165,7 @@ void producer_main(fq_frontend *fe) {
     fqdev::time_collect(t_ms, t_n, FQ_K_COUNT);
     fe->ms_inflate += t_ms[0]; fe->ms_lines += t_ms[1]; fe->ms_records += t_ms[2]; fe->ms_slots += t_ms[3]; fe->ms_tokenise += t_ms[1] + t_ms[2] + t_ms[3];
     fe->n_launch_inflate += (int64_t)t_n[0]; fe->n_chunks += 1;
-    fe->bam.ms_starts += t_ms[4]; fe->bam.ms_pairs += t_ms[5]; fe->bam.ms_fill += t_ms[6];
+    fe->bam.ms_starts += t_ms[4]; fe->bam.ms_pairs += t_ms[5]; fe->bam.ms_fill += t_ms[6]; fe->bam.ms_tags += t_ms[12];
     for (int k = 0; k < 5; ++k) fe->bam.K.ms[k] += t_ms[7 + k];
     fe->n_members += TB.members; fe->n_refused += TB.refused; fe->text_bytes += TB.text_bytes; fe->comp_bytes += TB.comp_bytes;
     {   // how many pairs follow this batch, by the files' sizes and the bytes a pair has taken so far (a hint: fq_align_text sizes a short first call's buffers by it)
@@ -1274,8 +1342,11 @@ struct HostBgzf {
 // The host's look at a BAM file: BGZF, magic, the header (it may span several members), where the records begin, and the first record that is
 // kept (neither secondary nor supplementary) -- its flag says paired or single-end, its l_seq sizes the rows.  Stands in for the open of the
 // reference's dormant bwa_read_bam (libbwa/bwaseqio.c:90-142).  FQ_OK, or FQ_EIO with out->error.
-extern "C" int fq_bam_probe(const char *path, fq_bam_probe_t *out) {
+static int probe_bam(const char *path, const fq_bam_select_t *sel, fq_bam_probe_t *out, std::string *header_text) {
   if (!path || !out) return FQ_EINVAL;
+  std::vector<uint32_t> ids;                     // (--bam_rg: "kept" is then what the tag body says, on the whole record)
+  pack_bam_ids(sel, &ids);
+  std::vector<uint8_t> rec;
   memset(out, 0, sizeof *out);
   out->first_flag = -1;
   auto fail = [&](const std::string &m) { snprintf(out->error, sizeof out->error, "%s: %s", path, m.c_str()); return FQ_EIO; };
@@ -1297,6 +1368,7 @@ extern "C" int fq_bam_probe(const char *path, fq_bam_probe_t *out) {
   if ((uint64_t)l_text > (uint64_t)sb.st_size * 1100 + 65536) return fail("the header's text length is not one this file can hold");      // (DEFLATE expands by 1032 at most)
   std::vector<uint8_t> text(l_text);
   if (l_text && !z.read(text.data(), l_text)) return fail(why("the header"));
+  if (header_text) header_text->assign((const char *)text.data(), text.size());
   {   // @HD ... SO:value
     const std::string t((const char *)text.data(), text.size());
     if (t.compare(0, 3, "@HD") == 0) {
@@ -1327,24 +1399,63 @@ extern "C" int fq_bam_probe(const char *path, fq_bam_probe_t *out) {
     const uint32_t bs = le32(fx);
     if (bs < 32 || bs > FQB_MAX_BLOCK || !z.read(fx + 4, 32)) break;
     const uint32_t flag = fx[18] | (uint32_t)fx[19] << 8;
-    if (!(flag & 0x900u)) {
+    bool kept = !(flag & 0x900u), whole = false;
+    if (kept && !ids.empty()) {
+      rec.resize((size_t)bs + 4);
+      memcpy(rec.data(), fx, 36);
+      if (!z.read(rec.data() + 36, bs - 32)) break;
+      whole = true;
+      uint32_t k = 0, oq = 0, unsel = 0;
+      (void)fq_bam_tags_record(rec.data(), ids.data(), 0, &k, &oq, &unsel);      // (a walk that fails: the stream's own walk refuses the record)
+      kept = k != 0;
+    }
+    if (kept) {
       const int32_t l = (int32_t)std::min<uint32_t>(le32(fx + 20), 0x7fffffffu);
       if (out->first_flag >= 0) { out->first_l_seq = std::max(out->first_l_seq, l); break; }      // (the second kept record of a paired stream: the rows hold the first pair's longer read, as the FASTQ path's do)
       out->first_flag = (int32_t)flag; out->paired = (int32_t)(flag & 1u); out->first_l_seq = l; out->first_l_name = fx[12];
       if (!out->paired) break;
     }
-    if (!z.read(nullptr, bs - 32)) break;
+    if (!whole && !z.read(nullptr, bs - 32)) break;
   }
+  return FQ_OK;
+}
+extern "C" int fq_bam_probe(const char *path, fq_bam_probe_t *out) { return probe_bam(path, nullptr, out, nullptr); }
+extern "C" int fq_bam_probe_select(const char *path, const fq_bam_select_t *sel, fq_bam_probe_t *out) { return probe_bam(path, sel, out, nullptr); }
+// The ID values of the header's @RG lines, in the header's order, each with its NUL, one behind the other in ids[cap]; *n_ids of them take *bytes
+// (FQ_ELIMIT where cap is smaller: call again).  FQ_EIO as fq_bam_probe, which this runs.
+extern "C" int fq_bam_read_groups(const char *path, char *ids, int64_t cap, int32_t *n_ids, int64_t *bytes) {
+  if (!path || !n_ids || !bytes || cap < 0 || (cap && !ids)) return FQ_EINVAL;
+  fq_bam_probe_t pr;
+  std::string text, all;
+  *n_ids = 0; *bytes = 0;
+  if (const int rc = probe_bam(path, nullptr, &pr, &text)) return rc;
+  for (size_t at = 0; at < text.size();) {
+    size_t eol = text.find('\n', at);
+    if (eol == std::string::npos) eol = text.size();
+    if (text.compare(at, 4, "@RG\t") == 0) {
+      for (size_t f = at + 3; f < eol;) {          // (f: at a tab)
+        size_t g = text.find('\t', f + 1);
+        if (g == std::string::npos || g > eol) g = eol;
+        if (text.compare(f + 1, 3, "ID:") == 0) { all.append(text, f + 4, g - f - 4); all.push_back('\0'); ++*n_ids; break; }
+        f = g;
+      }
+    }
+    at = eol + 1;
+  }
+  *bytes = (int64_t)all.size();
+  if ((int64_t)all.size() > cap) return FQ_ELIMIT;
+  if (!all.empty()) memcpy(ids, all.data(), all.size());
   return FQ_OK;
 }
 
 // One BAM file -> the batches fq_frontend_open gives for the two FASTQ texts its records transcode to (include/fastquick_amd.h).
 // collate_mem < 0: mates are adjacent (fq_frontend_open_bam); otherwise they are found by name, and the records waiting for theirs take so many bytes at most.
-static int open_bam(int device, const char *bam, int32_t batch_pairs, int64_t chunk_pairs, int32_t slot_mode, int32_t max_read_len, int64_t collate_mem, fq_frontend_t **out) {
+static int open_bam(int device, const char *bam, int32_t batch_pairs, int64_t chunk_pairs, int32_t slot_mode, int32_t max_read_len, int64_t collate_mem, const fq_bam_select_t *sel, fq_frontend_t **out) {
   if (!bam || !out || batch_pairs < 1 || chunk_pairs < batch_pairs || slot_mode < 0 || slot_mode > 2 || max_read_len < 16 || max_read_len > 4096) return FQ_EINVAL;
   *out = nullptr;
   fq_bam_probe_t pr;
-  if (const int rc = fq_bam_probe(bam, &pr)) return rc;
+  if (sel && (sel->n_ids < 0 || (sel->n_ids && !sel->ids))) return FQ_EINVAL;
+  if (const int rc = probe_bam(bam, sel, &pr, nullptr)) return rc;
   if (!pr.has_eof_block) fprintf(stderr, "WARNING - %s: no BGZF end-of-file block at the end of the file: it may be truncated\n", bam);
   struct StatesGuard { fqdev::State *s[3] = {nullptr, nullptr, nullptr}; bool armed = true; ~StatesGuard() { if (armed) for (fqdev::State *x : s) if (x) fqdev::state_destroy(x); } } guard;
   std::unique_ptr<fq_frontend> fe(new fq_frontend);
@@ -1355,6 +1466,7 @@ static int open_bam(int device, const char *bam, int32_t batch_pairs, int64_t ch
   fe->slot_mode = fe->n_files == 1 ? FQ_FASTQ_SLOTS_FRESH : slot_mode;
   fe->bam.on = true; fe->bam.n_ref = pr.n_ref; fe->bam.paired = pr.paired; fe->bam.first_off = (uint64_t)pr.rec_off;
   fe->bam.K.on = collate_mem >= 0; fe->bam.K.mem = collate_mem >= 0 ? (uint64_t)collate_mem : 0;
+  fe->bam.W.select(sel);
   const double l_name = pr.first_flag >= 0 ? (double)pr.first_l_name : 20.0, l_seq = pr.first_flag >= 0 ? (double)pr.first_l_seq : 151.0;
   for (int e = 0; e < fe->n_files; ++e) {
     FileSide &F = fe->f[e];
@@ -1393,16 +1505,26 @@ static int open_bam(int device, const char *bam, int32_t batch_pairs, int64_t ch
   return FQ_OK;
 }
 extern "C" int fq_frontend_open_bam(int device, const char *bam, int32_t batch_pairs, int64_t chunk_pairs, int32_t slot_mode, int32_t max_read_len, fq_frontend_t **out) {
-  return open_bam(device, bam, batch_pairs, chunk_pairs, slot_mode, max_read_len, -1, out);
+  return open_bam(device, bam, batch_pairs, chunk_pairs, slot_mode, max_read_len, -1, nullptr, out);
+}
+extern "C" int fq_frontend_open_bam_select(int device, const char *bam, int32_t batch_pairs, int64_t chunk_pairs, int32_t slot_mode, int32_t max_read_len, const fq_bam_select_t *sel, fq_frontend_t **out) {
+  return open_bam(device, bam, batch_pairs, chunk_pairs, slot_mode, max_read_len, -1, sel, out);
+}
+extern "C" int fq_frontend_open_bam_collate_select(int device, const char *bam, int32_t batch_pairs, int64_t chunk_pairs, int32_t slot_mode, int32_t max_read_len, int64_t collate_mem_bytes, const fq_bam_select_t *sel,
+                                                   fq_frontend_t **out) {
+  if (collate_mem_bytes < 0) return FQ_EINVAL;
+  return open_bam(device, bam, batch_pairs, chunk_pairs, slot_mode, max_read_len, collate_mem_bytes, sel, out);
 }
 extern "C" int fq_frontend_open_bam_collate(int device, const char *bam, int32_t batch_pairs, int64_t chunk_pairs, int32_t slot_mode, int32_t max_read_len, int64_t collate_mem_bytes, fq_frontend_t **out) {
   if (collate_mem_bytes < 0) return FQ_EINVAL;
-  return open_bam(device, bam, batch_pairs, chunk_pairs, slot_mode, max_read_len, collate_mem_bytes, out);
+  return open_bam(device, bam, batch_pairs, chunk_pairs, slot_mode, max_read_len, collate_mem_bytes, nullptr, out);
 }
 
 // Kernels (a)-(c) on their own (tests, measurement): a payload in host memory, cut into members where the caller says.
-extern "C" int fq_bam_transcode_device(int device, const uint8_t *payload, size_t n, const int64_t *member_off, int64_t n_members, int32_t n_ref, int64_t first_record, int32_t paired,
-                                       uint8_t *text1, size_t cap1, uint8_t *text2, size_t cap2, uint32_t *starts, int64_t starts_cap, fq_bam_transcode_t *out) {
+static int bam_transcode_device(int device, const uint8_t *payload, size_t n, const int64_t *member_off, int64_t n_members, int32_t n_ref, int64_t first_record, int32_t paired,
+                                uint8_t *text1, size_t cap1, uint8_t *text2, size_t cap2, uint32_t *starts, int64_t starts_cap, const fq_bam_select_t *sel, fq_bam_tag_counts_t *counts, fq_bam_transcode_t *out) {
+  if (counts) memset(counts, 0, sizeof *counts);
+  if (sel && (sel->n_ids < 0 || (sel->n_ids && !sel->ids))) return FQ_EINVAL;
   if (!out || (n && !payload) || n > 0xfff00000ull || first_record < 0 || (uint64_t)first_record > n || n_members < 0 || (n_members && !member_off)) return FQ_EINVAL;
   memset(out, 0, sizeof *out);
   DevScope scope(device);
@@ -1410,6 +1532,7 @@ extern "C" int fq_bam_transcode_device(int device, const uint8_t *payload, size_
   int rc = FQ_OK;
   {
     BamWork W;
+    W.select(sel);
     // (payload and texts are allocated to the byte: under the host-loop build a kernel body that reads behind the payload or writes behind a text is a sanitizer's finding)
     DevMem d_pay, d_text[2];
     if (!d_pay.alloc(std::max<size_t>(n, 1))) return FQ_ENOMEM;
@@ -1425,7 +1548,8 @@ extern "C" int fq_bam_transcode_device(int device, const uint8_t *payload, size_
     if (rc) return rc;
     out->records = R.n_rec; out->kept = R.n_kept; out->units = R.n_units; out->used_records = R.used_rec; out->paired = R.paired; out->chain_repairs = R.repairs;
     out->text_len[0] = (int64_t)R.text_len[0]; out->text_len[1] = (int64_t)R.text_len[1]; out->chain_end = R.chain_end; out->carry_from = R.carry_from; out->end_flag = R.end_flag;
-    out->bad_record = R.bad == FQB_NO_BAD ? -1 : (int64_t)(R.bad >> 3); out->bad_kind = R.bad == FQB_NO_BAD ? 0 : (int32_t)(R.bad & 7);
+    out->bad_record = R.bad == FQB_NO_BAD ? -1 : (int64_t)fqb_bad_ord(R.bad); out->bad_kind = R.bad == FQB_NO_BAD ? 0 : (int32_t)fqb_bad_kind(R.bad);
+    if (counts) { counts->unselected = R.n_unsel; counts->oq_records = R.n_oq; }
     if (starts && R.n_rec) {
       if ((int64_t)R.n_rec > starts_cap) return FQ_ELIMIT;
       if (fqdev::d2h(starts, W.starts.p, 4 * (size_t)R.n_rec) || fqdev::sync()) return FQ_ENODEV;
@@ -1443,14 +1567,28 @@ extern "C" int fq_bam_transcode_device(int device, const uint8_t *payload, size_
     uint64_t ln[FQ_K_COUNT] = {0};
     fqdev::time_collect(ms, ln, FQ_K_COUNT);
     out->ms_starts = ms[4]; out->ms_pairs = ms[5]; out->ms_fill = ms[6];
+    if (counts) counts->ms_tags = ms[12];
   }
   return rc;
+}
+extern "C" int fq_bam_transcode_device(int device, const uint8_t *payload, size_t n, const int64_t *member_off, int64_t n_members, int32_t n_ref, int64_t first_record, int32_t paired,
+                                       uint8_t *text1, size_t cap1, uint8_t *text2, size_t cap2, uint32_t *starts, int64_t starts_cap, fq_bam_transcode_t *out) {
+  return bam_transcode_device(device, payload, n, member_off, n_members, n_ref, first_record, paired, text1, cap1, text2, cap2, starts, starts_cap, nullptr, nullptr, out);
+}
+extern "C" int fq_bam_transcode_device_select(int device, const uint8_t *payload, size_t n, const int64_t *member_off, int64_t n_members, int32_t n_ref, int64_t first_record, int32_t paired,
+                                              uint8_t *text1, size_t cap1, uint8_t *text2, size_t cap2, uint32_t *starts, int64_t starts_cap, const fq_bam_select_t *sel, fq_bam_tag_counts_t *counts,
+                                              fq_bam_transcode_t *out) {
+  return bam_transcode_device(device, payload, n, member_off, n_members, n_ref, first_record, paired, text1, cap1, text2, cap2, starts, starts_cap, sel, counts, out);
 }
 // The collating chunk loop on its own (tests, measurement): the payload is taken up in chunks of members_per_chunk members each, as the front end
 // takes up a stream -- the record a chunk's end cuts off leads the next chunk's payload, the records waiting for their mates are held in HBM --, and
 // both texts are written chunk after chunk.
-extern "C" int fq_bam_collate_device(int device, const uint8_t *payload, size_t n, const int64_t *member_off, int64_t n_members, int64_t members_per_chunk, int32_t n_ref, int64_t first_record,
-                                     int32_t paired, int64_t collate_mem_bytes, uint8_t *text1, size_t cap1, uint8_t *text2, size_t cap2, fq_bam_collate_t *out) {
+static int bam_collate_device(int device, const uint8_t *payload, size_t n, const int64_t *member_off, int64_t n_members, int64_t members_per_chunk, int32_t n_ref, int64_t first_record,
+                              int32_t paired, int64_t collate_mem_bytes, uint8_t *text1, size_t cap1, uint8_t *text2, size_t cap2, const fq_bam_select_t *sel, fq_bam_tag_counts_t *counts, fq_bam_collate_t *out) {
+  if (counts) memset(counts, 0, sizeof *counts);
+  if (sel && (sel->n_ids < 0 || (sel->n_ids && !sel->ids))) return FQ_EINVAL;
+  std::vector<uint32_t> ids;
+  pack_bam_ids(sel, &ids);
   if (!out || (n && !payload) || n > 0xfff00000ull || first_record < 0 || (uint64_t)first_record > n || n_members < 0 || (n_members && !member_off) || collate_mem_bytes < 0 || paired < -1 || paired > 1) return FQ_EINVAL;
   memset(out, 0, sizeof *out);
   out->bad_record = -1;
@@ -1460,7 +1598,14 @@ extern "C" int fq_bam_collate_device(int device, const uint8_t *payload, size_t 
     for (uint64_t p = (uint64_t)first_record; p + 36 <= n;) {
       const uint32_t bs = le32(payload + p), flag = payload[p + 18] | (uint32_t)payload[p + 19] << 8;
       if (bs < 32 || bs > FQB_MAX_BLOCK) break;
-      if (!(flag & 0x900u)) { paired = (int32_t)(flag & 1u); break; }
+      bool kept = !(flag & 0x900u);
+      if (kept && !ids.empty()) {                 // (under a selection, as the probe: the tag body on the whole record)
+        if (p + 4 + (uint64_t)bs > n) break;
+        uint32_t k = 0, oq = 0, unsel = 0;
+        (void)fq_bam_tags_record(payload + p, ids.data(), 0, &k, &oq, &unsel);
+        kept = k != 0;
+      }
+      if (kept) { paired = (int32_t)(flag & 1u); break; }
       p += 4 + (uint64_t)bs;
     }
   }
@@ -1472,6 +1617,7 @@ extern "C" int fq_bam_collate_device(int device, const uint8_t *payload, size_t 
   BamWork W;
   BamHeld K;
   K.on = true; K.mem = (uint64_t)collate_mem_bytes;
+  W.select(sel);
   std::vector<uint8_t> carry;                    // the record the last chunk's end cut off
   uint64_t ord0 = 0, text_at[2] = {0, 0};
   uint8_t *host[2] = {text1, text2};
@@ -1497,7 +1643,8 @@ extern "C" int fq_bam_collate_device(int device, const uint8_t *payload, size_t 
     if (rc) return fail(rc);
     out->chunks += 1; out->records += R.n_rec; out->kept += R.n_kept; out->pairs += R.n_units; out->end_flag = R.end_flag;
     out->chain_end = (int64_t)(lo + R.chain_end - cl);
-    if (R.bad != FQB_NO_BAD) { out->bad_record = (int64_t)(R.bad >> 3); out->bad_kind = (int32_t)(R.bad & 7); break; }
+    if (counts) { counts->unselected += R.n_unsel; counts->oq_records += R.n_oq; }
+    if (R.bad != FQB_NO_BAD) { out->bad_record = (int64_t)fqb_bad_ord(R.bad); out->bad_kind = (int32_t)fqb_bad_kind(R.bad); break; }
     if (R.end_flag == FQB_SEG_CORRUPT) break;
     uint8_t *text[2] = {nullptr, nullptr};
     const int sides = R.paired ? 2 : 1;
@@ -1520,11 +1667,26 @@ extern "C" int fq_bam_collate_device(int device, const uint8_t *payload, size_t 
     uint64_t ln[FQ_K_COUNT] = {0};
     fqdev::time_collect(ms, ln, FQ_K_COUNT);
     out->ms_keys += ms[7]; out->ms_sort += ms[8]; out->ms_match += ms[9]; out->ms_units += ms[10]; out->ms_hold += ms[11];
+    if (counts) counts->ms_tags += ms[12];
+  }
+  if (counts && K.n && W.tags && W.use_oq && out->bad_record < 0) {      // (the orphans' OQ values were read by nobody)
+    std::vector<uint32_t> hoq(K.n);
+    if (fqdev::d2h(hoq.data(), K.oq[K.cur].p, 4 * (size_t)K.n) || fqdev::sync()) return FQ_ENODEV;
+    for (uint32_t v : hoq) if (v) --counts->oq_records;
   }
   out->text_len[0] = (int64_t)text_at[0]; out->text_len[1] = (int64_t)text_at[1];
   out->orphans = K.n; out->held_peak_records = K.peak_n; out->held_peak_bytes = K.peak_bytes;
   out->ms_collate = out->ms_keys + out->ms_sort + out->ms_match + out->ms_units + out->ms_hold;
   return FQ_OK;
+}
+extern "C" int fq_bam_collate_device(int device, const uint8_t *payload, size_t n, const int64_t *member_off, int64_t n_members, int64_t members_per_chunk, int32_t n_ref, int64_t first_record,
+                                     int32_t paired, int64_t collate_mem_bytes, uint8_t *text1, size_t cap1, uint8_t *text2, size_t cap2, fq_bam_collate_t *out) {
+  return bam_collate_device(device, payload, n, member_off, n_members, members_per_chunk, n_ref, first_record, paired, collate_mem_bytes, text1, cap1, text2, cap2, nullptr, nullptr, out);
+}
+extern "C" int fq_bam_collate_device_select(int device, const uint8_t *payload, size_t n, const int64_t *member_off, int64_t n_members, int64_t members_per_chunk, int32_t n_ref, int64_t first_record,
+                                            int32_t paired, int64_t collate_mem_bytes, uint8_t *text1, size_t cap1, uint8_t *text2, size_t cap2, const fq_bam_select_t *sel, fq_bam_tag_counts_t *counts,
+                                            fq_bam_collate_t *out) {
+  return bam_collate_device(device, payload, n, member_off, n_members, members_per_chunk, n_ref, first_record, paired, collate_mem_bytes, text1, cap1, text2, cap2, sel, counts, out);
 }
 extern "C" void fq_frontend_close(fq_frontend_t *fe) {
   if (!fe) return;
@@ -1600,6 +1762,7 @@ extern "C" void fq_frontend_stats(const fq_frontend_t *fe, fq_frontend_stats_t *
   s->bam_orphans = fe->bam.K.orphans; s->bam_held_peak_records = fe->bam.K.peak_n; s->bam_held_peak_bytes = fe->bam.K.peak_bytes;
   s->ms_bam_collate = fe->bam.K.ms[0] + fe->bam.K.ms[1] + fe->bam.K.ms[2] + fe->bam.K.ms[3] + fe->bam.K.ms[4];
   s->ms_bam_starts = fe->bam.ms_starts; s->ms_bam_pairs = fe->bam.ms_pairs; s->ms_bam_fill = fe->bam.ms_fill; s->ms_transcode = s->ms_bam_starts + s->ms_bam_pairs + s->ms_bam_fill;
+  s->bam_unselected = fe->bam.unselected; s->bam_oq_records = fe->bam.oq_records; s->ms_bam_tags = fe->bam.ms_tags; s->bam_empty_chunks = fe->bam.empty_chunks;
 }
 // batch accessors
 extern "C" int32_t fq_text_batch_pairs(const fq_text_batch_t *b) { return b ? b->n_pairs : 0; }

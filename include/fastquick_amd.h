@@ -336,6 +336,9 @@ typedef struct {
   int64_t bam_orphans;                   /* collation: kept records whose mate the stream does not hold (left out; known at the end of the stream) */
   int64_t bam_held_peak_records, bam_held_peak_bytes;   /* ... the most records that waited for their mates behind a chunk, and their bytes (what collate_mem bounds) */
   double ms_bam_collate;                 /* ... device time of the collation kernels: name keys, sort, match, units, held gather */
+  int64_t bam_unselected, bam_oq_records; /* --bam_rg: records (neither secondary nor supplementary) of another read group; --bam_oq: records whose quality line was taken from OQ */
+  double ms_bam_tags;                    /* ... device time of the kernel that walks the auxiliary fields (inside ms_bam_pairs, and so inside ms_transcode) */
+  int64_t bam_empty_chunks;              /* BAM input: chunks that held records but no kept one (all skipped, or of other read groups: a selected group that begins late in the file) */
 } fq_frontend_stats_t;
 /* BAM input.  The reference refuses --bam_in (src/BwtMapper.cpp:185-187); the interface these stand in for is its dormant bwa_read_bam
  * (libbwa/bwaseqio.c:90-142).  A BAM file X means the FASTQ texts T1 / T2 its records transcode to: records with flag 0x100 or
@@ -366,7 +369,7 @@ typedef struct {
   int64_t records, kept, pairs, orphans; /* records walked; kept; pairs written; kept records left without a mate */
   int64_t held_peak_records, held_peak_bytes;   /* the most that waited behind a chunk */
   int64_t text_len[2], chain_end;        /* chain_end: where the whole records end in the payload */
-  int64_t bad_record;                    /* the first refusal: ordinal (-1: none) and kind -- fq_bam_transcode_t's, and 7: a second record of a name and side before the mate of the first */
+  int64_t bad_record;                    /* the first refusal: ordinal (-1: none) and kind -- fq_bam_transcode_t's (1-6; 8, 9 with _select), and 7: a second record of a name and side before the mate of the first */
   int32_t bad_kind, paired, chunks, end_flag;
   double ms_collate, ms_keys, ms_sort, ms_match, ms_units, ms_hold;   /* device time of the collation kernels, and by kernel */
   char error[256];
@@ -383,7 +386,7 @@ typedef struct {
 typedef struct {
   int64_t records, kept, units, used_records, text_len[2];
   int64_t chain_end, carry_from;         /* where the whole records end; where what a following payload must begin with starts (an unpaired last kept record) */
-  int64_t bad_record;                    /* the first refusal: the record's ordinal (-1: none) and FQB_BAD_* kind: 1 mixed, 2 l_seq == 0, 3 fields, 4 name byte, 5 mates, 6 names */
+  int64_t bad_record;                    /* the first refusal: the record's ordinal (-1: none) and FQB_BAD_* kind: 1 mixed, 2 l_seq == 0, 3 fields, 4 name byte, 5 mates, 6 names (7: collation only); (_select) 8 auxiliary fields, 9 OQ */
   int32_t bad_kind, paired, chain_repairs, end_flag;   /* end_flag: 0 the payload ends with a record, 1 inside one, 2 at a block_size that is none */
   double ms_starts, ms_pairs, ms_fill;
 } fq_bam_transcode_t;
@@ -391,6 +394,29 @@ int fq_bam_probe(const char *path, fq_bam_probe_t *out);
 int fq_frontend_open_bam(int device, const char *bam, int32_t batch_pairs, int64_t chunk_pairs, int32_t slot_mode, int32_t max_read_len, fq_frontend_t **out);
 int fq_bam_transcode_device(int device, const uint8_t *payload, size_t n, const int64_t *member_off, int64_t n_members, int32_t n_ref, int64_t first_record, int32_t paired,
                             uint8_t *text1, size_t cap1, uint8_t *text2, size_t cap2, uint32_t *starts, int64_t starts_cap, fq_bam_transcode_t *out);
+/* Read groups and original qualities (`--bam_rg`, `--bam_oq`; DESIGN.md 5d''): the auxiliary fields of every record that is neither secondary nor
+ * supplementary are walked (SAM specification 4.2.4; the first RG and the first OQ decide).  With n_ids > 0 a record is kept only if its RG:Z value
+ * equals one of ids[] in length and bytes: the batches are those of the file that holds the skipped and the selected records alone, refusals naming
+ * ordinals over all records.  With use_oq a kept record that has OQ:Z prints those bytes as its quality line (reversed under 0x10).  Refusal kinds 8
+ * (the fields cannot be walked) and 9 (OQ does not fit the read: its length is not l_seq, or a byte outside 0x21..0x7e).  sel == NULL, or no ID and
+ * no use_oq: the entry without _select, kernel for kernel.
+ * fq_bam_probe_select: paired, first_* and first_flag are the first kept record's under the selection; the file is inflated on the host up to it.
+ * fq_bam_read_groups: the ID values of the header's @RG lines, each with its NUL, one behind the other in ids[cap]; FQ_ELIMIT (with *n_ids and
+ *   *bytes set) where cap is too small.
+ * counts (or NULL): records not selected, records whose OQ was used, the tag kernel's device time. */
+typedef struct { const char *const *ids; int32_t n_ids; int32_t use_oq; } fq_bam_select_t;
+typedef struct { int64_t unselected, oq_records; double ms_tags; } fq_bam_tag_counts_t;
+int fq_bam_probe_select(const char *path, const fq_bam_select_t *sel, fq_bam_probe_t *out);
+int fq_bam_read_groups(const char *path, char *ids, int64_t cap, int32_t *n_ids, int64_t *bytes);
+int fq_frontend_open_bam_select(int device, const char *bam, int32_t batch_pairs, int64_t chunk_pairs, int32_t slot_mode, int32_t max_read_len, const fq_bam_select_t *sel, fq_frontend_t **out);
+int fq_frontend_open_bam_collate_select(int device, const char *bam, int32_t batch_pairs, int64_t chunk_pairs, int32_t slot_mode, int32_t max_read_len, int64_t collate_mem_bytes, const fq_bam_select_t *sel,
+                                        fq_frontend_t **out);
+int fq_bam_transcode_device_select(int device, const uint8_t *payload, size_t n, const int64_t *member_off, int64_t n_members, int32_t n_ref, int64_t first_record, int32_t paired,
+                                   uint8_t *text1, size_t cap1, uint8_t *text2, size_t cap2, uint32_t *starts, int64_t starts_cap, const fq_bam_select_t *sel, fq_bam_tag_counts_t *counts,
+                                   fq_bam_transcode_t *out);
+int fq_bam_collate_device_select(int device, const uint8_t *payload, size_t n, const int64_t *member_off, int64_t n_members, int64_t members_per_chunk, int32_t n_ref, int64_t first_record,
+                                 int32_t paired, int64_t collate_mem_bytes, uint8_t *text1, size_t cap1, uint8_t *text2, size_t cap2, const fq_bam_select_t *sel, fq_bam_tag_counts_t *counts,
+                                 fq_bam_collate_t *out);
 int fq_frontend_open(int device, const char *fq1, const char *fq2, int32_t batch_pairs, int64_t chunk_pairs, int32_t slot_mode, int32_t max_read_len, fq_frontend_t **out);
 int64_t fq_frontend_next(fq_frontend_t *fe, fq_text_batch_t **out);
 void fq_frontend_release(fq_frontend_t *fe, fq_text_batch_t *b);

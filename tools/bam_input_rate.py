@@ -3,6 +3,10 @@
 (trimmed to 60..150 bases, Illumina-style names of varying length, with a comment in the FASTQ files; qualities over 40 values), written as an
 unaligned BAM and as two BGZF FASTQ files --, the BAM kernels' times and chain_repairs (profiles/bam_input.txt).
     python tools/bam_input_rate.py [--pairs N] [--uniform] [--only bam|fastq|collate] [--collate] [--far F] [--workdir DIR] [--root CHECKOUT]
+                                   [--tagged] [--bam_rg ID]... [--bam_oq]
+--tagged: the BAM legs read XT.bam -- the same records with NM, RG:Z (four groups g0..g3 interleaved pair by pair), OQ:Z (the qualities as they were; QUAL capped at 25, as a
+recalibration would leave it) and a B:S array, about 190 auxiliary bytes a record -- in place of X.bam; --bam_rg / --bam_oq (DESIGN.md 5d'', profiles/bam_tags.txt): the
+options of fq_frontend_open_bam_select on it, the tag kernel's time and the counts in the line;
 --collate: a third leg (DESIGN.md 5d', profiles/bam_collate.txt) -- the same records in a coordinate-like order (the permutation of tests/test_bam_collate.py's seeded
 stream: second mates a geometric distance behind their first, a fraction --far of them anywhere, 3 % supplementary copies, 1 % of the pairs without a mate) through
 fq_frontend_open_bam_collate, and through fq_bam_collate_device for the collation kernels' time by kernel;
@@ -27,6 +31,9 @@ ap.add_argument("--far", type=float, default=0.02, help="the fraction of second 
 ap.add_argument("--workdir")
 ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ap.add_argument("--reps", type=int, default=3)
+ap.add_argument("--tagged", action="store_true", help="the BAM legs read the file whose records carry RG (four groups interleaved) and OQ")
+ap.add_argument("--bam_rg", action="append", default=[], help="select this read group of the tagged file (g0..g3; repeatable)")
+ap.add_argument("--bam_oq", action="store_true", help="quality lines from OQ")
 a = ap.parse_args()
 sys.path.insert(0, os.path.abspath(a.root))
 from fastquick_amd import api, synth  # noqa: E402
@@ -40,6 +47,9 @@ X = os.path.join(work, "X_%s.bam" % key)
 fq = [os.path.join(work, "T%d_%s.fq.gz" % (e + 1, key)) for e in range(2)]
 S = os.path.join(work, "S_%s_%g.bam" % (key, a.far))
 collate = a.collate or a.only == "collate"
+tagged = a.tagged or a.bam_rg or a.bam_oq
+XT = os.path.join(work, "XT_%s.bam" % key)
+GROUPS = 4
 
 
 def bgzf_payload(path):
@@ -116,6 +126,28 @@ try:
         print("files written in %.0f s: %d pairs, X.bam %.1f MB, T1 %.1f MB, T2 %.1f MB" % (time.time() - t0, n, os.path.getsize(X) / 1e6, os.path.getsize(fq[0]) / 1e6, os.path.getsize(fq[1]) / 1e6),
               flush=True)
 
+    if tagged and not os.path.exists(XT):
+        t0 = time.time()
+        pay = bgzf_payload(X)
+        text = b"@HD\tVN:1.6\tSO:unsorted\n" + b"".join(b"@RG\tID:g%d\tSM:s\n" % k for k in range(GROUPS))
+        out, p, i = [b"BAM\1" + struct.pack("<i", len(text)) + text + pay[8:22]], 22, 0      # (X's header: no text, one reference "1": 22 bytes)
+        extra = b"ZBBS" + struct.pack("<I", 4) + struct.pack("<4H", 1, 2, 3, 4)
+        while p < len(pay):
+            bs = struct.unpack_from("<I", pay, p)[0]
+            r = pay[p:p + 4 + bs]
+            L = struct.unpack_from("<I", r, 20)[0]
+            q = np.frombuffer(r, dtype=np.uint8, count=L, offset=4 + bs - L)
+            body = r[4:4 + bs - L] + np.minimum(q, 25).tobytes() + b"NMC\0" + b"RGZg%d\0" % (i // 2 % GROUPS) + b"OQZ" + (q + 33).tobytes() + b"\0" + extra
+            out.append(struct.pack("<I", len(body)) + body)
+            p += 4 + bs; i += 1
+        with open(XT, "wb") as fh:
+            fh.write(synth.bgzf_compress(b"".join(out), threads=16, level=6))
+        print("tagged file written in %.0f s: XT.bam %.1f MB" % (time.time() - t0, os.path.getsize(XT) / 1e6), flush=True)
+    if tagged:
+        X = XT
+    n_sel = sum(1 for i in range(n) if "g%d" % (i % GROUPS) in a.bam_rg) if a.bam_rg else n
+    opts = dict(rg=a.bam_rg, oq=a.bam_oq) if a.bam_rg or a.bam_oq else {}      # (a checkout from before the options takes none)
+
     n_S = None
     if collate:
         t0 = time.time()
@@ -141,10 +173,12 @@ try:
     print("library of %s ; FASTQUICK_BAM_FILL=%s" % (os.path.abspath(a.root), os.environ.get("FASTQUICK_BAM_FILL", "(a wavefront per record)")), flush=True)
     for rep in range(a.reps):
         if a.only not in ("fastq", "collate"):
-            dt, st = run(lambda: api.BamFrontEnd(X, batch_pairs=262144, chunk_pairs=4 * 262144, slot_mode=0, max_read_len=160))
+            dt, st = run(lambda: api.BamFrontEnd(X, batch_pairs=262144, chunk_pairs=4 * 262144, slot_mode=0, max_read_len=160, **opts), n_sel)
             print("BAM   rep %d: %.3f s, %.2f M pairs/s ; inflate %.1f ms, starts %.1f, pairs %.1f, fill %.1f, tokenise %.1f ; chunks %d, repairs %d, records %d, wait_reader %.0f ms" % (
-                rep, dt, n / dt / 1e6, st["ms_inflate"], st["ms_bam_starts"], st["ms_bam_pairs"], st["ms_bam_fill"], st["ms_tokenise"], st["chunks"], st["chain_repairs"], st["bam_records"],
-                st["ms_wait_reader"]), flush=True)
+                rep, dt, n_sel / dt / 1e6, st["ms_inflate"], st["ms_bam_starts"], st["ms_bam_pairs"], st["ms_bam_fill"], st["ms_tokenise"], st["chunks"], st["chain_repairs"], st["bam_records"],
+                st["ms_wait_reader"]) + (" ; --bam_rg %s%s: tags %.1f ms (%.2f ms per million records), %d records unselected, %d with OQ, %.2f M records/s walked" % (
+                    ",".join(a.bam_rg) or "-", " --bam_oq" if a.bam_oq else "", st["ms_bam_tags"], st["ms_bam_tags"] / (st["bam_records"] / 1e6), st["bam_unselected"], st["bam_oq_records"],
+                    st["bam_records"] / dt / 1e6) if opts else ""), flush=True)
         if collate:
             dt, st = run(lambda: api.BamFrontEnd(S, batch_pairs=262144, chunk_pairs=4 * 262144, slot_mode=0, max_read_len=160, collate_mem=4 << 30), n_S)
             print("COLL  rep %d: %.3f s, %.2f M pairs/s ; inflate %.1f ms, starts %.1f, keep %.1f, collate %.1f, fill %.1f, tokenise %.1f ; chunks %d, repairs %d, records %d, orphans %d, held peak %d records %.1f MB, "
