@@ -128,6 +128,16 @@ class BamTranscode(C.Structure):      # fq_bam_transcode_t
                 ("ms_starts", C.c_double), ("ms_pairs", C.c_double), ("ms_fill", C.c_double)]
 
 
+class PopconOpts(C.Structure):      # fq_popcon_opts_t
+    _fields_ = [("num_pc", C.c_int32), ("within_ancestry", C.c_int32), ("disable_sanity_check", C.c_int32), ("fix_pc", C.c_int32), ("fix_alpha", C.c_int32), ("host_eval", C.c_int32),
+                ("device", C.c_int32), ("host_threads", C.c_int32), ("fix_pc_values", C.c_double * 8), ("fix_alpha_value", C.c_double), ("epsilon", C.c_double), ("known_af", C.c_char_p)]
+
+
+class PopconResult(C.Structure):      # fq_popcon_result_t
+    _fields_ = [("alpha", C.c_double), ("pc1", C.c_double * 8), ("pc2", C.c_double * 8), ("llk1", C.c_double), ("llk0", C.c_double), ("n_eval", C.c_int64),
+                ("n_marker", C.c_int32), ("markers_used", C.c_int32), ("num_pc", C.c_int32), ("avg_depth", C.c_double), ("sd_depth", C.c_double)]
+
+
 EXPORTS = ["fq_default_opts", "fq_index_build", "fq_index_load", "fq_index_destroy", "fq_index_l_pac",
            "fq_index_n_contigs", "fq_index_contig", "fq_ctx_create", "fq_ctx_destroy", "fq_ctx_last_error",
            "fq_ctx_set_debug", "fq_align_batch", "fq_batch_upload", "fq_align_resident", "fq_sam_header",
@@ -140,7 +150,9 @@ EXPORTS = ["fq_default_opts", "fq_index_build", "fq_index_load", "fq_index_destr
            "fq_text_batch_pairs", "fq_text_batch_first_name", "fq_align_text", "fq_text_batch_fetch", "fq_bam_probe", "fq_frontend_open_bam", "fq_bam_transcode_device", "fq_frontend_open_bam_collate", "fq_bam_collate_device",
            "fq_bam_probe_select", "fq_bam_read_groups", "fq_frontend_open_bam_select", "fq_frontend_open_bam_collate_select", "fq_bam_transcode_device_select", "fq_bam_collate_device_select",
            "fq_ctx_set_emit", "fq_sam_device_last", "fq_sam_device_bytes", "fq_ctx_attach_qc", "fq_ctx_attach_bam", "fq_bgzf_deflate_device", "fq_bgzf_deflate_device_mode", "fq_huffman_lengths_device", "fq_bam_set_deflate", "fq_bam_deflate_stats",
-           "fq_bam_create_sorted", "fq_bam_sort_stats", "fq_bam_sort_stats_at_close", "fq_bam_sort_run_entries", "fq_sort_keys_device"]
+           "fq_bam_create_sorted", "fq_bam_sort_stats", "fq_bam_sort_stats_at_close", "fq_bam_sort_run_entries", "fq_sort_keys_device",
+           "fq_popcon_default_opts", "fq_popcon_create", "fq_popcon_set_pileup_file", "fq_popcon_set_pileup_arrays", "fq_popcon_llk", "fq_popcon_marker_llk", "fq_popcon_run", "fq_popcon_result",
+           "fq_popcon_write", "fq_popcon_last_error", "fq_popcon_destroy", "fq_popcon_marker_index", "fq_popcon_marker_alleles", "fq_qc_piles"]
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)
 EMIT_SAM = 1
 
@@ -276,6 +288,21 @@ def load_library(path: str | None = None):
     L.fq_bam_add_last.argtypes = [C.c_void_p, C.c_void_p]
     L.fq_bam_close.argtypes = [C.c_void_p]
     _libs[path] = L
+    if hasattr(L, "fq_popcon_create"):      # (the host-loop library of the CPU test tier is built from the alignment sources alone)
+        L.fq_popcon_default_opts.argtypes = [C.POINTER(PopconOpts)]
+        L.fq_popcon_default_opts.restype = None
+        L.fq_popcon_create.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(PopconOpts), C.POINTER(C.c_void_p)]
+        L.fq_popcon_set_pileup_file.argtypes = [C.c_void_p, C.c_char_p]
+        L.fq_popcon_set_pileup_arrays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+        L.fq_popcon_llk.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.fq_popcon_marker_llk.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fq_popcon_run.argtypes = [C.c_void_p]
+        L.fq_popcon_result.argtypes = [C.c_void_p, C.POINTER(PopconResult)]
+        L.fq_popcon_write.argtypes = [C.c_void_p, C.c_char_p]
+        L.fq_popcon_last_error.argtypes = [C.c_void_p]
+        L.fq_popcon_last_error.restype = C.c_char_p
+        L.fq_popcon_destroy.argtypes = [C.c_void_p]
+        L.fq_popcon_destroy.restype = None
     return L
 
 
@@ -1123,3 +1150,74 @@ class BamFrontEnd(DeviceFrontEnd):
         if self.collate_mem is not None:
             return self.L.fq_frontend_open_bam_collate(device, bam.encode(), batch_pairs, chunk_pairs, slot_mode, max_read_len, self.collate_mem, C.byref(self.h))
         return self.L.fq_frontend_open_bam(device, bam.encode(), batch_pairs, chunk_pairs, slot_mode, max_read_len, C.byref(self.h))
+
+
+class Popcon:
+    """The contamination and ancestry estimate of `FASTQuick pop+con` (fq_popcon_*): VerifyBamID2's ContaminationEstimator on a pileup.  The likelihood runs in
+    the kernels of csrc/fq_popcon.h on `device`, or -- host_eval -- in the host loop over the same statement (the reference's doubles bit for bit)."""
+
+    def __init__(self, svd_prefix: str | None = None, ud: str | None = None, mu: str | None = None, bed: str | None = None, num_pc: int = 4, within_ancestry: bool = False,
+                 disable_sanity_check: bool = False, fix_pc=None, fix_alpha: float | None = None, known_af: str | None = None, epsilon: float = 1e-8, host_eval: bool = False,
+                 device: int = 0, host_threads: int = 0, lib=None):
+        self.L = lib or load_library()
+        o = PopconOpts()
+        self.L.fq_popcon_default_opts(C.byref(o))
+        o.num_pc, o.within_ancestry, o.disable_sanity_check, o.host_eval, o.device, o.host_threads, o.epsilon = num_pc, int(within_ancestry), int(disable_sanity_check), int(host_eval), device, host_threads, epsilon
+        if fix_pc is not None:
+            o.fix_pc = 1
+            for i, v in enumerate(list(fix_pc)[:8]):
+                o.fix_pc_values[i] = v
+        if fix_alpha is not None:
+            o.fix_alpha, o.fix_alpha_value = 1, fix_alpha
+        if known_af:
+            o.known_af = known_af.encode()
+        self.num_pc = num_pc
+        self.h = C.c_void_p()
+        enc = lambda s: s.encode() if s else None      # noqa: E731
+        rc = self.L.fq_popcon_create(enc(svd_prefix), enc(ud), enc(mu), enc(bed), C.byref(o), C.byref(self.h))
+        if rc:
+            raise FastquickError("fq_popcon_create failed (%d): %s" % (rc, self.L.fq_popcon_last_error(None).decode()))
+
+    def _check(self, rc, what):
+        if rc:
+            raise FastquickError("%s failed (%d): %s" % (what, rc, self.L.fq_popcon_last_error(self.h).decode()))
+
+    def set_pileup_file(self, path: str):
+        self._check(self.L.fq_popcon_set_pileup_file(self.h, path.encode()), "fq_popcon_set_pileup_file")
+
+    def set_pileup_arrays(self, marker, base, qual):
+        """base i (a character code) with quality character qual[i] lies on marker[i], a row of the .bed; pileup order per marker"""
+        m = np.ascontiguousarray(marker, dtype=np.int32)
+        b = np.ascontiguousarray(base, dtype=np.uint8)
+        q = np.ascontiguousarray(qual, dtype=np.uint8)
+        assert m.shape == b.shape == q.shape and m.ndim == 1
+        self._check(self.L.fq_popcon_set_pileup_arrays(self.h, m.ctypes.data, b.ctypes.data, q.ctypes.data, m.size), "fq_popcon_set_pileup_arrays")
+
+    def llk(self, points):
+        """ComputeMixLLKs at each row of points: PC1[num_pc], PC2[num_pc], alpha"""
+        p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2 * self.num_pc + 1)
+        out = np.zeros(p.shape[0], dtype=np.float64)
+        self._check(self.L.fq_popcon_llk(self.h, p.ctypes.data, p.shape[0], out.ctypes.data), "fq_popcon_llk")
+        return out
+
+    def marker_llk(self, point, n_marker: int):
+        p = np.ascontiguousarray(point, dtype=np.float64).reshape(2 * self.num_pc + 1)
+        out = np.zeros(n_marker, dtype=np.float64)
+        self._check(self.L.fq_popcon_marker_llk(self.h, p.ctypes.data, out.ctypes.data), "fq_popcon_marker_llk")
+        return out
+
+    def run(self):
+        self._check(self.L.fq_popcon_run(self.h), "fq_popcon_run")
+        r = PopconResult()
+        self._check(self.L.fq_popcon_result(self.h, C.byref(r)), "fq_popcon_result")
+        k = r.num_pc
+        return {"alpha": r.alpha, "pc1": list(r.pc1)[:k], "pc2": list(r.pc2)[:k], "llk1": r.llk1, "llk0": r.llk0, "n_eval": r.n_eval, "n_marker": r.n_marker,
+                "markers_used": r.markers_used, "avg_depth": r.avg_depth, "sd_depth": r.sd_depth}
+
+    def write(self, out_prefix: str):
+        self._check(self.L.fq_popcon_write(self.h, out_prefix.encode()), "fq_popcon_write")
+
+    def close(self):
+        if self.h:
+            self.L.fq_popcon_destroy(self.h)
+            self.h = None

@@ -8,6 +8,7 @@
 // files of StatCollector (<out_prefix>.InsertSizeTable .Pileup .DepthDist ... .Summary) are written in both modes (fq_qc_*) when the
 // index carries its .SelectedSite.vcf / .dbSNP.subset.vcf / .gc.  Flank lengths and the original reference (for @SQ and the genome
 // size) come from <index_prefix>.FASTQuick.fa.param as `FASTQuick index` wrote it (src/FASTQuick.cpp:376-465).
+#include <cmath>
 #include <sys/stat.h>
 #include <unistd.h>
 
@@ -27,6 +28,20 @@
 #include <vector>
 
 #include "../../include/fastquick_amd.h"
+
+// The estimator's entries are weak references here: the host-loop library of the CPU test tier (tests/emu) is built from the alignment sources alone, and
+// this file links against it too; there `pop+con` and `align --popcon_svd` say that the build has no estimator.
+#pragma weak fq_popcon_default_opts
+#pragma weak fq_popcon_create
+#pragma weak fq_popcon_set_pileup_file
+#pragma weak fq_popcon_set_pileup_arrays
+#pragma weak fq_popcon_marker_index
+#pragma weak fq_popcon_marker_alleles
+#pragma weak fq_popcon_run
+#pragma weak fq_popcon_result
+#pragma weak fq_popcon_write
+#pragma weak fq_popcon_last_error
+#pragma weak fq_popcon_destroy
 
 namespace {
 // part / worker files of a multi-device run: removed when the run dies (a finished run appends and removes them itself)
@@ -111,6 +126,9 @@ struct Args {
   int bam_l_seq = 0;          // ... the first kept record's length (fq_bam_probe): sizes the rows as a FASTQ file's first record does
   std::string fq_list, rg = "@RG\\tID:foo\\tSM:bar";   // runAlign's default --RG (src/FASTQuick.cpp:170)
   bool cal_dup = true;
+  std::string popcon_svd;     // --popcon_svd P: after the QC files, the contamination and ancestry estimate (pop+con) on the marker pileups the QC consumer holds; P.UD / P.mu / P.bed
+  bool popcon_within = false; // --popcon_within: pop+con's --WithinAncestry
+  int popcon_numpc = 4;       // --popcon_numpc: pop+con's --NumPC
   double frac = 1.0;    // --frac_samp: gap_opt_t::frac (libbwa/bwtaln.c:47), the share of the records that is kept
   int read_len = 151;   // gap_opt_t::read_len (libbwa/bwtaln.c:48): the reference sizes its read buffers from it and has no flag for it
 };
@@ -119,8 +137,10 @@ int usage() {
   fprintf(stderr, "Usage: FASTQuick_amd align --index_prefix P --fastq_1 R1.fq[.gz] [--fastq_2 R2.fq[.gz]] | --fq_list LIST | --bam_in X.bam [--collate [--collate_mem BYTES]] [--bam_rg ID]... [--bam_oq]  --out_prefix O [--sam_out | --sorted_bam [--sort_mem BYTES]] [--bam_deflate fixed|dynamic] [--RG STR] [--cal_dup]\n"
                   "                       [--q INT] [--n FLOAT|INT] [--kmer_thresh INT] [--o INT] [--e INT] [--i INT] [--d INT] [--l INT] [--k INT]\n"
                   "                       [--m INT] [--R INT] [--N] [--L] [--I] [--max_isize INT] [--max_occ INT] [--is_sw] [--n_multi INT] [--N_multi INT]\n"
-                  "                       [--ap_prior FLOAT] [--force_isize] [--frac_samp FLOAT] [--t INT] [--chunk_pairs INT] [--batch_pairs INT] [--device INT | --devices LIST] [--read_len INT] [--clean_names] [--strict_reference] [--host_reader] [--host_consumers]\n"
-                  "       FASTQuick_amd index --ref REDUCED.FASTQuick.fa [--rollhash]\n");
+                  "                       [--ap_prior FLOAT] [--force_isize] [--frac_samp FLOAT] [--t INT] [--chunk_pairs INT] [--batch_pairs INT] [--device INT | --devices LIST] [--read_len INT] [--clean_names] [--strict_reference] [--host_reader] [--host_consumers] [--popcon_svd P [--popcon_within] [--popcon_numpc INT]]\n"
+                  "       FASTQuick_amd index --ref REDUCED.FASTQuick.fa [--rollhash]\n"
+                  "       FASTQuick_amd pop+con --PileupFile F --SVDPrefix P | --UDPath U --MeanPath M --BedPath B  --Output O [--NumPC INT] [--WithinAncestry] [--FixPC a:b:..] [--FixAlpha FLOAT] [--KnownAF F]\n"
+                  "                       [--DisableSanityCheck] [--Epsilon FLOAT] [--host_eval] [--device INT]\n");
   return 1;
 }
 
@@ -926,11 +946,50 @@ Merged open_merged(Run &R) {
   if (R.have_qc && fq_qc_create(R.wk[0].ix, R.pre.c_str(), A.out_prefix.c_str(), &R.qo, &M.qc)) die("cannot set up the QC consumer");
   return M;
 }
+// `align --popcon_svd P`: the estimate of `pop+con` straight from the run.  The marker pileups the QC consumer holds (what it has just printed as O.Pileup) go to the
+// estimator in memory: a base equal to the .bed's ref allele becomes '.' or ',' by strand, entries with a mapping quality below 13 or a base quality below 2 are left out
+// (min_mq and min_baseQ of the reference's BAM route, SimplePileupViewer.cpp:678-679).  No BAQ and no handling of overlapping mates: the result is that of
+// `pop+con --PileupFile` on the pileup converted the same way.  Writes O.selfSM and O.Ancestry and appends its line to O.Summary.
+struct PopconFeed { fq_popcon_t *p; std::vector<int32_t> marker; std::vector<char> base, qual; };
+void popcon_after_qc(const Args &A, fq_qc_t *qc, int device) {
+  if (A.popcon_svd.empty()) return;
+  if (!qc) die("--popcon_svd reads the QC consumer's marker pileups: the index needs its .SelectedSite.vcf");
+  if (!fq_popcon_create) die("--popcon_svd: this build of the library has no estimator");
+  fq_popcon_opts_t o;
+  fq_popcon_default_opts(&o);
+  o.num_pc = A.popcon_numpc;
+  o.within_ancestry = A.popcon_within;
+  o.device = device;
+  PopconFeed F;
+  if (fq_popcon_create(A.popcon_svd.c_str(), nullptr, nullptr, nullptr, &o, &F.p)) die(std::string("--popcon_svd: ") + fq_popcon_last_error(nullptr));
+  const int rc = fq_qc_piles(qc, [](void *user, const char *chrom, int32_t pos, int64_t n, const char *bases, const char *quals, const uint8_t *maq, const int8_t *base_qual) -> int {
+    PopconFeed &f = *(PopconFeed *)user;
+    const int32_t row = fq_popcon_marker_index(f.p, chrom, pos);
+    if (row < 0) return 0;
+    char ref = 0;
+    fq_popcon_marker_alleles(f.p, row, &ref, nullptr);
+    for (int64_t t = 0; t < n; ++t) {
+      if (maq[t] < 13 || base_qual[t] < 2) continue;
+      char c = bases[t];
+      if (toupper((unsigned char)c) == toupper((unsigned char)ref)) c = isupper((unsigned char)c) ? '.' : ',';
+      f.marker.push_back(row); f.base.push_back(c); f.qual.push_back(quals[t]);
+    }
+    return 0;
+  }, &F);
+  if (rc) die("--popcon_svd: walking the marker pileups failed");
+  auto fail = [&](const char *what) { const std::string m = std::string("--popcon_svd: ") + what + ": " + fq_popcon_last_error(F.p); die(m); };
+  if (fq_popcon_set_pileup_arrays(F.p, F.marker.data(), F.base.data(), F.qual.data(), (int64_t)F.marker.size())) fail("pileup");
+  if (fq_popcon_run(F.p)) fail("estimate");
+  if (fq_popcon_write(F.p, A.out_prefix.c_str())) fail("output");
+  fq_popcon_destroy(F.p);
+  mark("contamination and ancestry estimated");
+}
 void close_merged(Run &R, Merged &M) {   // ... and the workers' objects go
   M.out.flush();
   if (M.out.bam && !close_bam_file(R.A, M.out.bam)) die("closing " + R.A.bam_file() + " failed");
   if (M.qc) {
     if (fq_qc_write(M.qc)) die("writing the QC files failed");
+    popcon_after_qc(R.A, M.qc, R.devices[0]);
     fq_qc_destroy(M.qc);
   }
   release_join();
@@ -974,6 +1033,7 @@ void run_one_device(Run &R) {
   if (bam_bad) die("closing " + A.bam_file() + " failed");
   if (qc_bad) die("writing the QC files failed");
   mark("QC files written");
+  popcon_after_qc(A, K.qc, R.devices[0]);
   if (K.qc) { fq_qc_t *qc = K.qc; release_later([qc] { fq_qc_destroy(qc); mark("QC consumer released"); }); }      // (beside the contexts' release)
   release_join();
   fq_index_destroy(K.ix);
@@ -1029,9 +1089,80 @@ void run_list_over_devices(Run &R) {
 }
 }  // namespace
 
+// `FASTQuick pop+con` (VerifyBamID/vb2Main.cpp runVB2): flags of the reference's names and meanings
+static int popcon_main(int argc, char **argv) {
+  if (!fq_popcon_create) die("pop+con: this build of the library has no estimator");
+  fq_popcon_opts_t o;
+  fq_popcon_default_opts(&o);
+  std::string pileup = "Empty", svd = "Empty", out = "result", ud = "Empty", mu = "Empty", bed = "Empty", known_af;
+  for (int i = 2; i < argc; ++i) {
+    const std::string f = argv[i];
+    auto need = [&]() -> const char * { if (i + 1 >= argc) die("missing value for " + f); return argv[++i]; };
+    if (f == "--PileupFile") pileup = need();
+    else if (f == "--SVDPrefix") svd = need();
+    else if (f == "--Output") out = need();
+    else if (f == "--NumPC") o.num_pc = atoi(need());
+    else if (f == "--WithinAncestry") o.within_ancestry = 1;
+    else if (f == "--DisableSanityCheck") o.disable_sanity_check = 1;
+    else if (f == "--FixPC") {   // PC1:PC2:.. (vb2Main.cpp:165-182)
+      fprintf(stderr, "NOTICE - you specified --fixPC, this will overide dynamic estimation of PCs\n");
+      const std::string v = need();
+      size_t a = 0;
+      int n = 0;
+      while (a <= v.size()) {
+        const size_t b = std::min(v.find(':', a), v.size());
+        if (n < 8) o.fix_pc_values[n] = atof(v.substr(a, b - a).c_str());
+        ++n;
+        a = b + 1;
+      }
+      o.fix_pc = n;
+    }
+    else if (f == "--FixAlpha") { o.fix_alpha_value = atof(need()); o.fix_alpha = 1; }
+    else if (f == "--KnownAF") known_af = need();
+    else if (f == "--Epsilon") o.epsilon = atof(need());
+    else if (f == "--UDPath") ud = need();
+    else if (f == "--MeanPath") mu = need();
+    else if (f == "--BedPath") bed = need();
+    else if (f == "--host_eval") o.host_eval = 1;
+    else if (f == "--device") o.device = atoi(need());
+    else if (f == "--Seed" || f == "--NumThread" || f == "--Reference") { need(); fprintf(stderr, "NOTICE - %s is accepted and ignored: the estimate draws no random number, sizes its own threads and reads no reference file\n", f.c_str()); }
+    else if (f == "--BamFile") die("--BamFile is not supported (the BAM route needs BAQ and htslib's overlap handling): give the pileup with --PileupFile");
+    else if (f == "--RefVCF") die("--RefVCF is not supported (the SVD files are made offline): give --SVDPrefix, and the pileup with --PileupFile");
+    else die("unknown option " + f);
+  }
+  if (o.num_pc > 4) die("--NumPC only permits as large as 4 PCs when using SVD files in ${verifybamID}/resource/ directory!");
+  if (o.fix_pc) {
+    if (o.fix_pc < o.num_pc) die("parameter --fixPC provided smaller dimension than parameter --numPC");
+    if (o.fix_pc > o.num_pc) fprintf(stderr, "WARNING - parameter --fixPC provided larger dimension than parameter --numPC and hence will be truncated\n");
+    o.fix_pc = 1;
+  } else if (o.fix_alpha && fabs(o.fix_alpha_value + 1.) <= 2.220446049250313e-16) o.fix_alpha = 0;   // (-1 is "not given" there)
+  if (svd == "Empty") {
+    if (ud == "Empty") die("--UDPath is required when --RefVCF is absent");
+    if (mu == "Empty") die("--MeanPath is required when --RefVCF is absent");
+    if (bed == "Empty") die("--BedPath is required when --RefVCF is absent");
+  }
+  if (pileup == "Empty") die("--BamFile or --PileupFile is required (--PileupFile here)");
+  if (!known_af.empty()) o.known_af = known_af.c_str();
+  if (!o.host_eval) fq_runtime_configure(0, 1);
+  fq_popcon_t *p = nullptr;
+  if (fq_popcon_create(svd == "Empty" ? nullptr : svd.c_str(), ud.c_str(), mu.c_str(), bed.c_str(), &o, &p)) die(fq_popcon_last_error(nullptr));
+  auto fail = [&](const char *what) { const std::string m = std::string(what) + ": " + fq_popcon_last_error(p); fq_popcon_destroy(p); die(m); };
+  if (fq_popcon_set_pileup_file(p, pileup.c_str())) fail("pileup");
+  if (fq_popcon_run(p)) fail("pop+con");
+  if (fq_popcon_write(p, out.c_str())) fail("output");
+  fq_popcon_result_t r;
+  fq_popcon_result(p, &r);
+  fprintf(stderr, "NOTICE - FREEMIX %g, %lld likelihood evaluations over %d of %d markers (%s)\n", r.alpha < 0.5 ? r.alpha : 1 - r.alpha, (long long)r.n_eval, r.markers_used, r.n_marker,
+          o.host_eval ? "host loop" : "device kernels");
+  fq_popcon_destroy(p);
+  fprintf(stderr, "NOTICE - Success!\n");
+  return 0;
+}
+
 int main(int argc, char **argv) {
   if (argc < 2) return usage();
   const std::string cmd = argv[1];
+  if (cmd == "pop+con") return popcon_main(argc, argv);
   if (cmd == "index") {
     std::string ref;
     int rollhash = 0;
@@ -1102,6 +1233,9 @@ int main(int argc, char **argv) {
     else if (f == "--collate") A.collate = true;
     else if (f == "--bam_rg") A.bam_rg.push_back(need(""));
     else if (f == "--bam_oq") A.bam_oq = true;
+    else if (f == "--popcon_svd") A.popcon_svd = need("");
+    else if (f == "--popcon_within") A.popcon_within = true;
+    else if (f == "--popcon_numpc") A.popcon_numpc = atoi(need(""));
     else if (f == "--collate_mem") { A.collate_mem = atoll(need("")); A.collate_mem_given = true; if (A.collate_mem < 0) die("--collate_mem must not be negative"); }
     else die("unknown option " + f);
   }
@@ -1117,6 +1251,8 @@ int main(int argc, char **argv) {
   if (!A.bam_rg.empty() && A.bam_in.empty()) die("--bam_rg selects read groups of a BAM file: it needs --bam_in (--RG names the output's group)");
   if (A.bam_oq && A.bam_in.empty()) die("--bam_oq reads the OQ qualities of a BAM file: it needs --bam_in");
   if (A.collate_mem_given && !A.collate) die("--collate_mem bounds what --collate holds: it needs --collate");
+  if (A.popcon_svd.empty() && (A.popcon_within || A.popcon_numpc != 4)) die("--popcon_within and --popcon_numpc shape the estimate of --popcon_svd: they need it");
+  if (A.popcon_numpc > 4 || A.popcon_numpc < 1) die("--popcon_numpc takes 1 to 4, as pop+con's --NumPC");
   if (A.out_prefix == "Empty") die("--out_prefix is required");
   if (A.index_prefix == "Empty") die("--index_prefix is required");
   R.inputs = read_inputs(A, !A.bam_in.empty() && probe_bam_input(A));

@@ -18,6 +18,8 @@
 #include <unistd.h>
 
 #include "fq_backend.h"
+#define FQ_PC_KERNELS
+#include "fq_popcon.h"
 
 namespace fqdev {
 
@@ -2038,6 +2040,89 @@ int launch_bam_chold(const FqBamCollateArgs &a) {
   hipLaunchKernelGGL(k_bam_chold, dim3(nblk(a.n, 4)), dim3(256), 0, g_stream, a);
   FQ_HIP(hipGetLastError());
   return 0;
+}
+
+// ---- pop+con: the mixture likelihood (fq_popcon.h) ----
+// The device arrays of an estimate.  pc_prepare uploads the pileup's characters as the host read them, scans the depths (launch_scan: plain and padded to
+// sixteen) and packs them with k_pc_prepare; an evaluation is then two launches (k_pc_llk, k_pc_sum) and one wait: the points and the sums lie in pinned
+// host memory the kernels read and write in place.
+struct PcDev {
+  FqPcPile pile{};
+  int max_points = 0;
+  std::vector<void *> owned;
+  double *out = nullptr;         // max_points x n_marker
+  double *pts = nullptr, *sums = nullptr;   // pinned
+};
+void pc_free(PcDev *d) {
+  if (!d) return;
+  for (void *p : d->owned) dfree(p);
+  hfree(d->pts);
+  hfree(d->sums);
+  delete d;
+}
+PcDev *pc_prepare(const FqPcPrepHost &h, int max_points) {
+  if (!g_cur) { g_err = "no device state bound"; return nullptr; }
+  if (h.n_marker <= 0 || h.n_q <= 0 || h.n_q > FQ_PC_MAXQ || h.n_pc < 0 || h.n_pc > FQ_PC_MAXPC || max_points < 1) { g_err = "pc_prepare: bad sizes"; return nullptr; }
+  PcDev *d = new PcDev;
+  d->max_points = max_points;
+  bool ok = true;
+  auto up = [&](const void *src, size_t bytes) -> void * {
+    void *p = dmalloc(bytes);
+    if (!p) { ok = false; return nullptr; }
+    d->owned.push_back(p);
+    if (src && bytes && h2d(p, src, bytes)) ok = false;
+    return p;
+  };
+  const int M = h.n_marker;
+  std::vector<uint32_t> padded((size_t)M);
+  uint64_t n_bytes = 0;
+  for (int i = 0; i < M; ++i) { padded[i] = (h.depth[i] + (FQ_PC_PAD - 1)) & ~(uint32_t)(FQ_PC_PAD - 1); n_bytes += padded[i]; }
+  uint32_t *depth = (uint32_t *)up(h.depth, (size_t)M * 4);
+  uint32_t *dpad = (uint32_t *)up(padded.data(), (size_t)M * 4);
+  uint64_t *off = (uint64_t *)up(nullptr, ((size_t)M + 1) * 8), *raw_off = (uint64_t *)up(nullptr, ((size_t)M + 1) * 8);
+  char *base = (char *)up(h.base, h.n_chars), *qual = (char *)up(h.qual, h.n_chars), *alt = (char *)up(h.alt, (size_t)M);
+  uint8_t *slot_of_q = (uint8_t *)up(h.slot_of_q, 256);
+  int8_t *q_of_slot = (int8_t *)up(h.q_of_slot, FQ_PC_MAXQ);
+  uint8_t *code = (uint8_t *)up(nullptr, n_bytes + FQ_PC_PAD), *skip = (uint8_t *)up(nullptr, (size_t)M);
+  double *ud = (double *)up(h.ud, (size_t)M * (h.n_pc ? h.n_pc : 1) * 8), *mean = (double *)up(h.mean, (size_t)M * 8);
+  double *af = (double *)up(h.known_af ? h.af : nullptr, (size_t)M * 8);
+  d->out = (double *)up(nullptr, (size_t)max_points * M * 8);
+  d->pts = (double *)hmalloc((size_t)max_points * FQ_PC_POINT * 8);
+  d->sums = (double *)hmalloc((size_t)max_points * 8);
+  if (!ok || !d->pts || !d->sums) { pc_free(d); return nullptr; }
+  if (launch_scan(depth, raw_off, (uint32_t)M) || launch_scan(dpad, off, (uint32_t)M)) { pc_free(d); return nullptr; }
+  FqPcPrepArgs a{};
+  a.n_marker = M; a.sanity = h.sanity; a.avg = h.avg; a.sd = h.sd;
+  a.depth = depth; a.off = off; a.raw_off = raw_off; a.base = base; a.qual = qual; a.alt = alt; a.slot_of_q = slot_of_q; a.code = code; a.skip = skip;
+  const uint64_t n_thr = n_bytes > (uint64_t)M ? n_bytes : (uint64_t)M;
+  hipLaunchKernelGGL(k_pc_prepare, dim3(nblk(n_thr, 256)), dim3(256), 0, g_stream, a, n_bytes);
+  if (hipGetLastError() != hipSuccess || sync()) { g_err = "k_pc_prepare failed: " + g_err; pc_free(d); return nullptr; }   // (the host arrays may go once this returns)
+  FqPcPile &P = d->pile;
+  P.n_marker = M; P.n_pc = h.n_pc; P.n_q = h.n_q; P.known_af = h.known_af;
+  P.depth = depth; P.off = off; P.code = code; P.skip = skip; P.q_of_slot = q_of_slot; P.ud = ud; P.mean = mean; P.af = af;
+  return d;
+}
+static int pc_launch(PcDev *d, const double *pts, int n) {
+  if (!d || n < 1 || n > d->max_points) { g_err = "pc_llk: point count out of range"; return -1; }
+  FQ_PRE();
+  memcpy(d->pts, pts, (size_t)n * FQ_PC_POINT * 8);
+  const unsigned nb = std::min(nblk((uint64_t)d->pile.n_marker, FQ_PC_PER_BLOCK), 1024u);
+  hipLaunchKernelGGL(k_pc_llk, dim3(nb, (unsigned)n), dim3(FQ_PC_BLOCK), 0, g_stream, d->pile, (const double *)d->pts, d->out);
+  FQ_HIP(hipGetLastError());
+  return 0;
+}
+int pc_llk(PcDev *d, const double *pts, int n, double *sums) {
+  if (int rc = pc_launch(d, pts, n)) return rc;
+  hipLaunchKernelGGL(k_pc_sum, dim3((unsigned)n), dim3(256), 0, g_stream, (const double *)d->out, d->pile.n_marker, d->sums);
+  FQ_HIP(hipGetLastError());
+  if (sync()) return -3;
+  memcpy(sums, d->sums, (size_t)n * 8);
+  return 0;
+}
+int pc_marker_llk(PcDev *d, const double *pt, double *per_marker) {
+  if (int rc = pc_launch(d, pt, 1)) return rc;
+  if (d2h(per_marker, d->out, (size_t)d->pile.n_marker * 8)) return -3;
+  return sync();
 }
 
 // dynamic-LDS limits of the kernels that ask for more than the default 64 KB: once per device (state_create)

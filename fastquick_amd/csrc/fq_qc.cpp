@@ -923,6 +923,28 @@ FileStat get_file(In &in) { FileStat F; F.NumRead = in.get<long long>(); F.NumBa
 void add_file(FileStat &a, const FileStat &b) { a.NumRead += b.NumRead; a.NumBase += b.NumBase; a.TotalFiltered += b.TotalFiltered; a.BwaUnmapped += b.BwaUnmapped; a.TotalMAPQ += b.TotalMAPQ; a.TotalRetained += b.TotalRetained; }
 }  // namespace
 
+// the marker pileups as GetPileup prints them (fq_qc_write's .Pileup: the same order of the markers, the same characters), with the entries' mapping and
+// base qualities as numbers beside them: what `align --popcon_svd` hands to the contamination estimate in memory
+extern "C" int fq_qc_piles(const fq_qc_t *q, fq_qc_pile_fn fn, void *user) {
+  if (!q || !fn) return FQ_EINVAL;
+  const int qualoffset = (q->o.mode & FQ_MODE_IL13) ? 64 : 33;
+  std::string bases, quals;
+  for (auto &chr : q->vcf_table)
+    for (auto &site : chr.second) {
+      const unsigned k = site.second;
+      const size_t n = q->seq_vec[k].size();
+      if (!n) continue;
+      bases.resize(n);
+      quals.resize(n);
+      for (size_t t = 0; t != n; ++t) {
+        bases[t] = (char)(q->strand_vec[k][t] ? toupper(q->seq_vec[k][t]) : tolower(q->seq_vec[k][t]));
+        quals[t] = char(q->qual_vec[k][t] + qualoffset);
+      }
+      if (int rc = fn(user, chr.first.c_str(), (int32_t)site.first, (int64_t)n, bases.data(), quals.data(), q->maq_vec[k].data(), (const int8_t *)q->qual_vec[k].data())) return rc;
+    }
+  return FQ_OK;
+}
+
 extern "C" int fq_qc_state_reset(fq_qc_t *q) {
   if (!q) return FQ_EINVAL;
   if (int rc = q->pull()) return rc;       // (what the device holds is dropped with the rest: pulled into the tables that are cleared below)

@@ -490,6 +490,11 @@ int fq_qc_begin_file(fq_qc_t *q, const char *fastq_1, const char *fastq_2);
 int fq_qc_add_last(fq_qc_t *q, fq_ctx_t *c);   /* the records of the context's last batch; call before the next fq_align_* on it */
 int fq_qc_end_file(fq_qc_t *q);
 int fq_qc_write(fq_qc_t *q);                   /* ProcessCore: writes the files (once, at the end) */
+/* The marker pileups the consumer holds, marker by marker in the order and with the characters of the .Pileup file (GetPileup, src/StatCollector.cpp:2030-2065:
+ * bases in upper case on the forward strand, qualities with the file's offset), and beside them each entry's mapping quality and base quality as numbers.
+ * A non-zero return of fn ends the walk and is returned.  (What `align --popcon_svd` feeds fq_popcon_set_pileup_arrays from.) */
+typedef int (*fq_qc_pile_fn)(void *user, const char *chrom, int32_t pos, int64_t n, const char *bases, const char *quals, const uint8_t *maq, const int8_t *base_qual);
+int fq_qc_piles(const fq_qc_t *q, fq_qc_pile_fn fn, void *user);
 /* The consumer over several ranks (StatCollector is one object per run in the reference: FileStatCollector sums per FASTQ pair,
  * src/StatCollector.h:46-62, AddFSC; tables filled by AddSingleAlignment / ProcessPairStatus, src/StatCollector.cpp:424-921).
  * Each rank feeds its shard of the input -- whole FASTQ pairs of a --fq_list, or reference batches of one pair -- to a consumer of
@@ -678,6 +683,51 @@ int fq_device_count(void);
 /* (tests) table t (0..5) of the read filter's bitmaps as fq_index_load left it on the device: 2^29 bytes into out -- what BwtIndexer keeps in
  * roll_hash_table[t] (src/BwtIndexer.cpp:96-160, 803-837), whether it came from .rollhash, from a list of bits or from the reference's 32-mers. */
 int fq_index_bitmap_fetch(const fq_index_t *ix, int32_t t, uint8_t *out);
+
+/* ---- pop+con: contamination (FREEMIX) and genetic-ancestry estimate ----
+ * Replaces `FASTQuick pop+con` (VerifyBamID2: VerifyBamID/vb2Main.cpp runVB2, ContaminationEstimator.{h,cpp}, the AmoebaMinimizer of MathGenMin.cpp:310-443)
+ * on a pileup (`--PileupFile`, SimplePileupViewer.cpp:767-846) or on pileups held in memory.  The likelihood (ContaminationEstimator.h:206-281) is evaluated
+ * by the kernels of fq_popcon.h, or -- host_eval -- by the host loop over the same statement, which reproduces the reference's doubles bit for bit. */
+typedef struct fq_popcon fq_popcon_t;
+typedef struct {
+  int32_t num_pc;               /* --NumPC (vb2Main.cpp: 4; at most 8 here) */
+  int32_t within_ancestry;      /* --WithinAncestry */
+  int32_t disable_sanity_check; /* --DisableSanityCheck */
+  int32_t fix_pc;               /* --FixPC given: fix_pc_values[0..num_pc) */
+  int32_t fix_alpha;            /* --FixAlpha given: fix_alpha_value */
+  int32_t host_eval;            /* 1: the likelihood on the host (no device is opened) */
+  int32_t device;               /* device ordinal of the kernels */
+  int32_t host_threads;         /* threads of the host evaluator (0: fq_host_cpus(), at most 16); the sum stays serial in marker order */
+  double fix_pc_values[8];
+  double fix_alpha_value;
+  double epsilon;               /* --Epsilon (1e-8) */
+  const char *known_af;         /* --KnownAF file or NULL */
+} fq_popcon_opts_t;
+typedef struct {
+  double alpha;                 /* globalAlpha as estimated (FREEMIX is alpha folded below 0.5) */
+  double pc1[8], pc2[8];        /* globalPC (contaminating sample), globalPC2 (intended sample) */
+  double llk1, llk0;            /* as the reference holds them: the negated log likelihoods */
+  int64_t n_eval;               /* likelihood evaluations of the run */
+  int32_t n_marker;             /* lines of the .UD (NumMarker) */
+  int32_t markers_used;         /* markers that add to the likelihood */
+  int32_t num_pc;
+  double avg_depth, sd_depth;
+} fq_popcon_result_t;
+void fq_popcon_default_opts(fq_popcon_opts_t *o);                 /* runVB2's defaults */
+/* ContaminationEstimator's constructor + ReadSVDMatrix (+ ReadAF): svd_prefix + .UD/.mu/.bed, or the three paths (--UDPath/--MeanPath/--BedPath) with svd_prefix NULL */
+int fq_popcon_create(const char *svd_prefix, const char *ud, const char *mu, const char *bed, const fq_popcon_opts_t *o, fq_popcon_t **out);
+int fq_popcon_set_pileup_file(fq_popcon_t *p, const char *path);  /* SimplePileupViewer::ReadPileup */
+/* pileups held in memory: base[i] with quality character qual[i] lies on marker[i] (a row of the .bed), in pileup order per marker; numBases is n, a site is a marker that has a base */
+int fq_popcon_set_pileup_arrays(fq_popcon_t *p, const int32_t *marker, const char *base, const char *qual, int64_t n);
+int32_t fq_popcon_marker_index(const fq_popcon_t *p, const char *chrom, int32_t pos);       /* row of the .bed that holds the site (1-based pos), the first if several; -1: none */
+int fq_popcon_marker_alleles(const fq_popcon_t *p, int32_t marker, char *ref, char *alt);  /* ChooseBed's pair of the row's site */
+int fq_popcon_llk(fq_popcon_t *p, const double *points, int32_t n_points, double *out);   /* ComputeMixLLKs at points of 2 * num_pc + 1 doubles: PC1, PC2, alpha */
+int fq_popcon_marker_llk(fq_popcon_t *p, const double *point, double *out);               /* (tests) the per-marker log(markerLK) of one point, NumMarker doubles */
+int fq_popcon_run(fq_popcon_t *p);                                /* IsSanityCheckOK (unless disabled) + OptimizeLLK; FQ_ELIMIT when the sanity check fails */
+int fq_popcon_result(const fq_popcon_t *p, fq_popcon_result_t *out);
+int fq_popcon_write(fq_popcon_t *p, const char *out_prefix);      /* O.selfSM (vb2Main.cpp:249-274), O.Ancestry, the line appended to O.Summary (ContaminationEstimator.cpp:104-138) */
+const char *fq_popcon_last_error(const fq_popcon_t *p);           /* (NULL p: the error of a failed fq_popcon_create on this thread) */
+void fq_popcon_destroy(fq_popcon_t *p);
 
 #ifdef __cplusplus
 }
