@@ -138,6 +138,16 @@ class PopconResult(C.Structure):      # fq_popcon_result_t
                 ("n_marker", C.c_int32), ("markers_used", C.c_int32), ("num_pc", C.c_int32), ("avg_depth", C.c_double), ("sd_depth", C.c_double)]
 
 
+class SvdOpts(C.Structure):      # fq_svd_opts_t
+    _fields_ = [("host_eval", C.c_int32), ("device", C.c_int32), ("host_threads", C.c_int32), ("max_iter", C.c_int32), ("tol", C.c_double)]
+
+
+class SvdResult(C.Structure):      # fq_svd_result_t
+    _fields_ = [("n_marker", C.c_int32), ("n_sample", C.c_int32), ("iterations", C.c_int32), ("residual", C.c_double), ("mu", C.POINTER(C.c_double)), ("ud", C.POINTER(C.c_double)),
+                ("v", C.POINTER(C.c_double)), ("sigma", C.c_double * 10), ("t_read", C.c_double), ("t_gram", C.c_double), ("t_iter", C.c_double), ("t_project", C.c_double),
+                ("t_write", C.c_double)]
+
+
 EXPORTS = ["fq_default_opts", "fq_index_build", "fq_index_load", "fq_index_destroy", "fq_index_l_pac",
            "fq_index_n_contigs", "fq_index_contig", "fq_ctx_create", "fq_ctx_destroy", "fq_ctx_last_error",
            "fq_ctx_set_debug", "fq_align_batch", "fq_batch_upload", "fq_align_resident", "fq_sam_header",
@@ -152,7 +162,8 @@ EXPORTS = ["fq_default_opts", "fq_index_build", "fq_index_load", "fq_index_destr
            "fq_ctx_set_emit", "fq_sam_device_last", "fq_sam_device_bytes", "fq_ctx_attach_qc", "fq_ctx_attach_bam", "fq_bgzf_deflate_device", "fq_bgzf_deflate_device_mode", "fq_huffman_lengths_device", "fq_bam_set_deflate", "fq_bam_deflate_stats",
            "fq_bam_create_sorted", "fq_bam_sort_stats", "fq_bam_sort_stats_at_close", "fq_bam_sort_run_entries", "fq_sort_keys_device",
            "fq_popcon_default_opts", "fq_popcon_create", "fq_popcon_set_pileup_file", "fq_popcon_set_pileup_arrays", "fq_popcon_llk", "fq_popcon_marker_llk", "fq_popcon_run", "fq_popcon_result",
-           "fq_popcon_write", "fq_popcon_last_error", "fq_popcon_destroy", "fq_popcon_marker_index", "fq_popcon_marker_alleles", "fq_qc_piles"]
+           "fq_popcon_write", "fq_popcon_last_error", "fq_popcon_destroy", "fq_popcon_marker_index", "fq_popcon_marker_alleles", "fq_qc_piles",
+           "fq_svd_default_opts", "fq_svd_create", "fq_svd_read_vcf", "fq_svd_set_genotypes", "fq_svd_gram", "fq_svd_run", "fq_svd_result", "fq_svd_write", "fq_svd_last_error", "fq_svd_destroy"]
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)
 EMIT_SAM = 1
 
@@ -303,6 +314,20 @@ def load_library(path: str | None = None):
         L.fq_popcon_last_error.restype = C.c_char_p
         L.fq_popcon_destroy.argtypes = [C.c_void_p]
         L.fq_popcon_destroy.restype = None
+    if hasattr(L, "fq_svd_create"):
+        L.fq_svd_default_opts.argtypes = [C.POINTER(SvdOpts)]
+        L.fq_svd_default_opts.restype = None
+        L.fq_svd_create.argtypes = [C.POINTER(SvdOpts), C.POINTER(C.c_void_p)]
+        L.fq_svd_read_vcf.argtypes = [C.c_void_p, C.c_char_p]
+        L.fq_svd_set_genotypes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p)]
+        L.fq_svd_gram.argtypes = [C.c_void_p, C.c_void_p]
+        L.fq_svd_run.argtypes = [C.c_void_p]
+        L.fq_svd_result.argtypes = [C.c_void_p, C.POINTER(SvdResult)]
+        L.fq_svd_write.argtypes = [C.c_void_p, C.c_char_p]
+        L.fq_svd_last_error.argtypes = [C.c_void_p]
+        L.fq_svd_last_error.restype = C.c_char_p
+        L.fq_svd_destroy.argtypes = [C.c_void_p]
+        L.fq_svd_destroy.restype = None
     return L
 
 
@@ -1220,4 +1245,77 @@ class Popcon:
     def close(self):
         if self.h:
             self.L.fq_popcon_destroy(self.h)
+            self.h = None
+
+
+class Svd:
+    """The SVD files of a reference panel (fq_svd_*): what `FASTQuick pop+con --RefVCF` (VerifyBamID2's SVDcalculator) makes.  The Gram matrix, the iteration's
+    step and the projection run in the kernels of csrc/fq_svd.h on `device`, or -- host_eval -- as host loops over the same statements."""
+
+    def __init__(self, host_eval: bool = False, device: int = 0, host_threads: int = 0, max_iter: int | None = None, tol: float | None = None, lib=None):
+        self.L = lib or load_library()
+        o = SvdOpts()
+        self.L.fq_svd_default_opts(C.byref(o))
+        o.host_eval, o.device, o.host_threads = int(host_eval), device, host_threads
+        if max_iter is not None:
+            o.max_iter = max_iter
+        if tol is not None:
+            o.tol = tol
+        self.h = C.c_void_p()
+        rc = self.L.fq_svd_create(C.byref(o), C.byref(self.h))
+        if rc:
+            raise FastquickError("fq_svd_create failed (%d): %s" % (rc, self.L.fq_svd_last_error(None).decode()))
+        self.n_sample = 0
+
+    def _check(self, rc, what):
+        if rc:
+            raise FastquickError("%s failed (%d): %s" % (what, rc, self.L.fq_svd_last_error(self.h).decode()))
+
+    def read_vcf(self, path: str):
+        self._check(self.L.fq_svd_read_vcf(self.h, path.encode()), "fq_svd_read_vcf")
+        r = SvdResult()
+        self.L.fq_svd_result(self.h, C.byref(r))
+        self.n_sample = r.n_sample
+        return r.n_marker, r.n_sample
+
+    def set_genotypes(self, G, sites=None, samples=None):
+        """G: markers x samples in -1 .. 2; sites: (chrom, pos, ref, alt) per marker; samples: the names"""
+        g = np.ascontiguousarray(G, dtype=np.int8)
+        M, N = g.shape
+        chrom = pos = ref = alt = names = None
+        if sites is not None:
+            chrom = (C.c_char_p * M)(*[s[0].encode() for s in sites])
+            pos = np.ascontiguousarray([s[1] for s in sites], dtype=np.int32)
+            ref = "".join(s[2] for s in sites).encode()
+            alt = "".join(s[3] for s in sites).encode()
+        if samples is not None:
+            names = (C.c_char_p * N)(*[s.encode() for s in samples])
+        self._check(self.L.fq_svd_set_genotypes(self.h, g.ctypes.data, M, N, chrom, pos.ctypes.data if pos is not None else None, ref, alt, names), "fq_svd_set_genotypes")
+        self.n_sample = N
+
+    def gram(self):
+        out = np.zeros((self.n_sample, self.n_sample), dtype=np.int32)
+        self._check(self.L.fq_svd_gram(self.h, out.ctypes.data), "fq_svd_gram")
+        return out
+
+    def run(self):
+        self._check(self.L.fq_svd_run(self.h), "fq_svd_run")
+        return self.result()
+
+    def result(self):
+        r = SvdResult()
+        self._check(self.L.fq_svd_result(self.h, C.byref(r)), "fq_svd_result")
+        M, N = r.n_marker, r.n_sample
+        if not r.v:
+            raise FastquickError("fq_svd_result: nothing has run")
+        return {"n_marker": M, "n_sample": N, "iterations": r.iterations, "residual": r.residual, "mu": np.ctypeslib.as_array(r.mu, (M,)).copy(),
+                "ud": np.ctypeslib.as_array(r.ud, (M, 10)).copy(), "v": np.ctypeslib.as_array(r.v, (N, 10)).copy(), "sigma": np.array(list(r.sigma)),
+                "seconds": {"read": r.t_read, "gram": r.t_gram, "iteration": r.t_iter, "projection": r.t_project, "write": r.t_write}}
+
+    def write(self, prefix: str):
+        self._check(self.L.fq_svd_write(self.h, prefix.encode()), "fq_svd_write")
+
+    def close(self):
+        if self.h:
+            self.L.fq_svd_destroy(self.h)
             self.h = None

@@ -42,6 +42,14 @@
 #pragma weak fq_popcon_write
 #pragma weak fq_popcon_last_error
 #pragma weak fq_popcon_destroy
+#pragma weak fq_svd_default_opts
+#pragma weak fq_svd_create
+#pragma weak fq_svd_read_vcf
+#pragma weak fq_svd_run
+#pragma weak fq_svd_result
+#pragma weak fq_svd_write
+#pragma weak fq_svd_last_error
+#pragma weak fq_svd_destroy
 
 namespace {
 // part / worker files of a multi-device run: removed when the run dies (a finished run appends and removes them itself)
@@ -140,7 +148,8 @@ int usage() {
                   "                       [--ap_prior FLOAT] [--force_isize] [--frac_samp FLOAT] [--t INT] [--chunk_pairs INT] [--batch_pairs INT] [--device INT | --devices LIST] [--read_len INT] [--clean_names] [--strict_reference] [--host_reader] [--host_consumers] [--popcon_svd P [--popcon_within] [--popcon_numpc INT]]\n"
                   "       FASTQuick_amd index --ref REDUCED.FASTQuick.fa [--rollhash]\n"
                   "       FASTQuick_amd pop+con --PileupFile F --SVDPrefix P | --UDPath U --MeanPath M --BedPath B  --Output O [--NumPC INT] [--WithinAncestry] [--FixPC a:b:..] [--FixAlpha FLOAT] [--KnownAF F]\n"
-                  "                       [--DisableSanityCheck] [--Epsilon FLOAT] [--host_eval] [--device INT]\n");
+                  "                       [--DisableSanityCheck] [--Epsilon FLOAT] [--host_eval] [--device INT]\n"
+                  "       FASTQuick_amd svd --RefVCF PANEL.vcf[.gz] [--Output P] [--host_eval] [--device INT]\n");
   return 1;
 }
 
@@ -1127,7 +1136,7 @@ static int popcon_main(int argc, char **argv) {
     else if (f == "--device") o.device = atoi(need());
     else if (f == "--Seed" || f == "--NumThread" || f == "--Reference") { need(); fprintf(stderr, "NOTICE - %s is accepted and ignored: the estimate draws no random number, sizes its own threads and reads no reference file\n", f.c_str()); }
     else if (f == "--BamFile") die("--BamFile is not supported (the BAM route needs BAQ and htslib's overlap handling): give the pileup with --PileupFile");
-    else if (f == "--RefVCF") die("--RefVCF is not supported (the SVD files are made offline): give --SVDPrefix, and the pileup with --PileupFile");
+    else if (f == "--RefVCF") die("--RefVCF is not supported here (`FASTQuick_amd svd --RefVCF` makes the SVD files): give their prefix with --SVDPrefix, and the pileup with --PileupFile");
     else die("unknown option " + f);
   }
   if (o.num_pc > 4) die("--NumPC only permits as large as 4 PCs when using SVD files in ${verifybamID}/resource/ directory!");
@@ -1159,10 +1168,46 @@ static int popcon_main(int argc, char **argv) {
   return 0;
 }
 
+// `FASTQuick pop+con --RefVCF` (vb2Main.cpp:119-131: SVDcalculator::ProcessRefVCF): P.UD, P.mu, P.V and P.bed of a reference panel; P defaults to the VCF's path
+static int svd_main(int argc, char **argv) {
+  if (!fq_svd_create) die("svd: this build of the library has no SVD calculator");
+  fq_svd_opts_t o;
+  fq_svd_default_opts(&o);
+  std::string vcf, out;
+  for (int i = 2; i < argc; ++i) {
+    const std::string f = argv[i];
+    auto need = [&]() -> const char * { if (i + 1 >= argc) die("missing value for " + f); return argv[++i]; };
+    if (f == "--RefVCF") vcf = need();
+    else if (f == "--Output") out = need();
+    else if (f == "--host_eval") o.host_eval = 1;
+    else if (f == "--device") o.device = atoi(need());
+    else die("unknown option " + f);
+  }
+  if (vcf.empty()) die("svd: --RefVCF is required");
+  if (out.empty()) out = vcf;
+  if (!o.host_eval) fq_runtime_configure(0, 1);
+  fq_svd_t *p = nullptr;
+  if (fq_svd_create(&o, &p)) die(fq_svd_last_error(nullptr));
+  auto fail = [&](const char *what) { const std::string m = std::string(what) + ": " + fq_svd_last_error(p); fq_svd_destroy(p); die(m); };
+  if (fq_svd_read_vcf(p, vcf.c_str())) fail("svd");
+  fq_svd_result_t r;
+  fq_svd_result(p, &r);
+  fprintf(stderr, "NOTICE - Number of Markers:%d\nNOTICE - Number of Individuals:%d\n", r.n_marker, r.n_sample);
+  if (fq_svd_run(p)) fail("svd");
+  if (fq_svd_write(p, out.c_str())) fail("output");
+  fq_svd_result(p, &r);
+  fprintf(stderr, "NOTICE - sigma_0 %g, %d iterations, residual %.3g (%s); read %.3f s, Gram %.3f s, iteration %.3f s, projection %.3f s, write %.3f s\n", r.sigma[0], r.iterations, r.residual,
+          o.host_eval ? "host loops" : "device kernels", r.t_read, r.t_gram, r.t_iter, r.t_project, r.t_write);
+  fq_svd_destroy(p);
+  fprintf(stderr, "NOTICE - Success!\n");
+  return 0;
+}
+
 int main(int argc, char **argv) {
   if (argc < 2) return usage();
   const std::string cmd = argv[1];
   if (cmd == "pop+con") return popcon_main(argc, argv);
+  if (cmd == "svd") return svd_main(argc, argv);
   if (cmd == "index") {
     std::string ref;
     int rollhash = 0;

@@ -20,6 +20,8 @@
 #include "fq_backend.h"
 #define FQ_PC_KERNELS
 #include "fq_popcon.h"
+#define FQ_SVD_KERNELS
+#include "fq_svd.h"
 
 namespace fqdev {
 
@@ -2122,6 +2124,79 @@ int pc_llk(PcDev *d, const double *pts, int n, double *sums) {
 int pc_marker_llk(PcDev *d, const double *pt, double *per_marker) {
   if (int rc = pc_launch(d, pt, 1)) return rc;
   if (d2h(per_marker, d->out, (size_t)d->pile.n_marker * 8)) return -3;
+  return sync();
+}
+
+// ---- svd: the SVD files of a reference panel (fq_svd.h) ----
+// The device arrays of a decomposition: the int8 genotypes sample-major, the Gram matrix, the means, t and q, the centred Gram matrix in double, and the
+// iteration's block.  svd_gram is four launches and one wait; an iteration step (svd_apply) is a copy up, one launch, a copy down and one wait.
+struct SvdDev {
+  int32_t n = 0, n_pad = 0;
+  int64_t m = 0, m_pad = 0;
+  int8_t *gt = nullptr;
+  int32_t *a = nullptr;
+  double *mu = nullptr, *tq = nullptr, *c = nullptr, *q = nullptr, *y = nullptr, *ud = nullptr;
+};
+void svd_free(SvdDev *d) {
+  if (!d) return;
+  dfree(d->gt); dfree(d->a); dfree(d->mu); dfree(d->tq); dfree(d->c); dfree(d->q); dfree(d->y); dfree(d->ud);
+  delete d;
+}
+SvdDev *svd_upload(const int8_t *gt, int32_t n, int32_t n_pad, int64_t m, int64_t m_pad, const double *mu) {
+  if (!g_cur) { g_err = "no device state bound"; return nullptr; }
+  if (n < 1 || m < 1 || m > FQ_SVD_MAX_MARKERS || n_pad < n || m_pad < m || n_pad % FQ_SVD_TILE || m_pad % FQ_SVD_TILE) { g_err = "svd_upload: bad sizes"; return nullptr; }
+  SvdDev *d = new SvdDev;
+  d->n = n; d->n_pad = n_pad; d->m = m; d->m_pad = m_pad;
+  const int32_t b = std::min<int32_t>(n, FQ_SVD_BLOCK_MAX);
+  d->gt = (int8_t *)dmalloc((size_t)n_pad * m_pad);
+  d->a = (int32_t *)dmalloc((size_t)n_pad * n_pad * 4);
+  d->mu = (double *)dmalloc((size_t)m * 8);
+  d->tq = (double *)dmalloc(((size_t)n + 1) * 8);
+  d->c = (double *)dmalloc((size_t)n * n * 8);
+  d->q = (double *)dmalloc((size_t)n * std::max<int32_t>(b, FQ_SVD_NPC) * 8);
+  d->y = (double *)dmalloc((size_t)n * b * 8);
+  d->ud = (double *)dmalloc((size_t)m * FQ_SVD_NPC * 8);
+  if (!d->gt || !d->a || !d->mu || !d->tq || !d->c || !d->q || !d->y || !d->ud) { svd_free(d); return nullptr; }
+  if (h2d(d->gt, gt, (size_t)n_pad * m_pad) || h2d(d->mu, mu, (size_t)m * 8) || sync()) { svd_free(d); return nullptr; }   // (the host arrays may go once this returns)
+  return d;
+}
+int svd_gram(SvdDev *d, int32_t *a_out) {
+  if (!d) { g_err = "svd_gram: no arrays"; return -1; }
+  FQ_PRE();
+  if (dzero(d->a, (size_t)d->n_pad * d->n_pad * 4)) return -3;
+  FqSvdGramArgs p{};
+  p.gt = d->gt; p.a = d->a; p.n_tiles = d->n_pad / FQ_SVD_TILE; p.m_pad = d->m_pad;
+  // few tile pairs (N small, M large): the markers are split over blocks until about a thousand are in flight, a wavefront keeping at least one instruction
+  const int64_t pairs = (int64_t)p.n_tiles * (p.n_tiles + 1) / 2, chunks = d->m_pad / FQ_SVD_TILE;
+  p.n_split = (int32_t)std::max<int64_t>(1, std::min<int64_t>({(1024 + pairs - 1) / pairs, (chunks + 3) / 4, 1024}));
+  hipLaunchKernelGGL(k_svd_gram, dim3((unsigned)pairs, (unsigned)p.n_split), dim3(256), 0, g_stream, p);
+  FQ_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_svd_tq, dim3((unsigned)d->n + 1), dim3(256), 0, g_stream, (const int8_t *)d->gt, d->m_pad, d->m, d->n, (const double *)d->mu, d->tq);
+  FQ_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_svd_centre, dim3(nblk((uint64_t)d->n * d->n, 256)), dim3(256), 0, g_stream, (const int32_t *)d->a, (size_t)d->n_pad, d->n, (const double *)d->tq, d->c);
+  FQ_HIP(hipGetLastError());
+  if (a_out) {
+    std::vector<int32_t> pad((size_t)d->n_pad * d->n_pad);
+    if (d2h(pad.data(), d->a, pad.size() * 4) || sync()) return -3;
+    for (int32_t j = 0; j < d->n; ++j) memcpy(a_out + (size_t)j * d->n, pad.data() + (size_t)j * d->n_pad, (size_t)d->n * 4);
+    return 0;
+  }
+  return sync();
+}
+int svd_apply(SvdDev *d, const double *q, int32_t b, double *y) {
+  if (!d || b < 1 || b > FQ_SVD_BLOCK_MAX || b > d->n) { g_err = "svd_apply: block width out of range"; return -1; }
+  if (h2d(d->q, q, (size_t)d->n * b * 8)) return -3;
+  hipLaunchKernelGGL(k_svd_apply, dim3(nblk((uint64_t)d->n, 8)), dim3(32, 8), 0, g_stream, (const double *)d->c, (const double *)d->q, d->n, b, d->y);
+  FQ_HIP(hipGetLastError());
+  if (d2h(y, d->y, (size_t)d->n * b * 8)) return -3;
+  return sync();
+}
+int svd_project(SvdDev *d, const double *v, double *ud) {
+  if (!d) { g_err = "svd_project: no arrays"; return -1; }
+  if (h2d(d->q, v, (size_t)d->n * FQ_SVD_NPC * 8)) return -3;
+  hipLaunchKernelGGL(k_svd_project, dim3(nblk((uint64_t)d->m, 128)), dim3(128), 0, g_stream, (const int8_t *)d->gt, d->m_pad, d->m, d->n, (const double *)d->q, (const double *)d->mu, d->ud);
+  FQ_HIP(hipGetLastError());
+  if (d2h(ud, d->ud, (size_t)d->m * FQ_SVD_NPC * 8)) return -3;
   return sync();
 }
 

@@ -320,3 +320,51 @@ def write_param(prefix_fa: str, ref: SynthRef, n_long: int) -> None:
         fh.write("NUM_VAR_SHORT\t%d\n" % (len(ref.names) - n_long))
         fh.write("SHORT_FLANK_LENGTH\t250\n")
         fh.write("LONG_FLANK_LENGTH\t1000\n")
+
+
+def panel_genotypes(M: int, N: int, seed: int) -> np.ndarray:
+    """Genotypes of a reference panel with population structure, markers x samples, int8 in {-1, 0, 1, 2} (what SVDcalculator::ReadVcf keeps per
+    sample: the best genotype, or -1 where no likelihood lies below 255).  Twelve groups, sample j in group j mod 12; per marker an ancestral
+    frequency U(0.1, 0.9), a group's frequency = ancestral + N(0, s_k) with s_k from 0.30 down to 0.06, clipped to [0.02, 0.98]; genotypes
+    Binomial(2, p); 0.2 % of the entries -1.  The groups' different drifts keep the leading singular values apart."""
+    rng = np.random.default_rng(seed)
+    K = 12
+    anc = rng.uniform(0.1, 0.9, M)
+    s = np.linspace(0.30, 0.06, K)
+    p = np.clip(anc[:, None] + rng.normal(0.0, 1.0, (M, K)) * s[None, :], 0.02, 0.98)
+    G = rng.binomial(2, p[:, np.arange(N) % K]).astype(np.int8)
+    G[rng.random((M, N)) < 0.002] = -1
+    return G
+
+
+def panel_sites(M: int):
+    """chromosome, position (1-based), ref, alt of marker i of a synthetic panel: the autosomes in order, positions ascending"""
+    per = (M + 21) // 22
+    return [(str(i // per + 1), 10000 + 137 * (i % per) + (i % 7), "ACGT"[i % 4], "ACGT"[(i + 1 + i // 4 % 3) % 4]) for i in range(M)]
+
+
+def panel_vcf(path: str, G: np.ndarray, fmt: str = "GT") -> np.ndarray:
+    """Writes the panel G (markers x samples) as a VCF whose FORMAT is `GT`, `PL` or `GL` (gzip when the path ends in .gz) and returns the genotypes
+    SVDcalculator::ReadVcf reads back from it: G itself, except that `GT` has no way to say -1 (`./.` reads as 0/0)."""
+    import gzip
+    M, N = G.shape
+    pl = {0: (0, 30, 50), 1: (50, 0, 50), 2: (50, 30, 0), -1: (255, 255, 255)}
+    lines = ["##fileformat=VCFv4.1\n", "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + "\t".join("S%04d" % j for j in range(N)) + "\n"]
+    for i, (chrom, pos, ref, alt) in enumerate(panel_sites(M)):
+        if fmt == "GT":
+            cells = [("./.", "0/0", "0|1" if (i + j) & 1 else "1/0", "1|1")[g + 1] for j, g in enumerate(G[i])]
+        elif fmt == "PL":
+            cells = ["0/0:%d,%d,%d" % pl[int(g)] for g in G[i]]
+        elif fmt == "GL":
+            cells = ["%.2f,%.2f,%.2f" % tuple(-0.1 * v - 0.04 for v in pl[int(g)]) for g in G[i]]      # (-10 x value, 30.4 say, truncates back to the PL)
+        else:
+            raise ValueError("fmt must be GT, PL or GL")
+        lines.append("%s\t%d\t.\t%s\t%s\t.\tPASS\t.\t%s\t%s\n" % (chrom, pos, ref, alt, "GT:" + fmt if fmt == "PL" else fmt, "\t".join(cells)))
+    data = "".join(lines).encode()
+    if path.endswith(".gz"):
+        with open(path, "wb") as raw, gzip.GzipFile(fileobj=raw, mode="wb", mtime=0) as gz:
+            gz.write(data)
+    else:
+        with open(path, "wb") as fh:
+            fh.write(data)
+    return np.where(G < 0, 0, G).astype(np.int8) if fmt == "GT" else G.copy()

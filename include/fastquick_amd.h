@@ -729,6 +729,46 @@ int fq_popcon_write(fq_popcon_t *p, const char *out_prefix);      /* O.selfSM (v
 const char *fq_popcon_last_error(const fq_popcon_t *p);           /* (NULL p: the error of a failed fq_popcon_create on this thread) */
 void fq_popcon_destroy(fq_popcon_t *p);
 
+/* ---- svd: the SVD files of a reference panel (P.UD, P.mu, P.V, P.bed) ----
+ * Replaces `FASTQuick pop+con --RefVCF` (VerifyBamID2: SVDcalculator::ProcessRefVCF, VerifyBamID/SVDcalculator.cpp:195-236, called from vb2Main.cpp:119-131 and
+ * bin/FASTQuick_template.sh:451).  The reference runs Eigen's JacobiSVD<MatrixXf> on the mean-centred markers x samples matrix; here the ten leading components
+ * come from the exact integer Gram matrix of the genotypes, centred in double, by block subspace iteration (csrc/fq_svd.h), in the kernels of
+ * fq_svd.h or -- host_eval -- as host loops over the same statements.  The sign of a component: its entry of V of largest magnitude is positive. */
+typedef struct fq_svd fq_svd_t;
+typedef struct {
+  int32_t host_eval;            /* 1: the five statements as host loops (no device is opened) */
+  int32_t device;               /* device ordinal of the kernels */
+  int32_t host_threads;         /* threads of the host loops (0: fq_host_cpus(), at most 16) */
+  int32_t max_iter;             /* cap of the iteration (2000): beyond it fq_svd_run is FQ_ELIMIT and nothing can be written */
+  double tol;                   /* the iteration stops when max over c < 10 of |C q_c - lambda_c q_c| <= tol * lambda_0 (1e-11) */
+} fq_svd_opts_t;
+typedef struct {
+  int32_t n_marker, n_sample;   /* kept markers, samples */
+  int32_t iterations;           /* steps of the iteration */
+  double residual;              /* the final residual, relative to lambda_0 */
+  const double *mu;             /* n_marker: the float means (Eigen's rowwise().mean(), SVDcalculator.cpp:211) as doubles */
+  const double *ud;             /* n_marker x 10: U diag(sigma) = X V (:218-226) */
+  const double *v;              /* n_sample x 10 (:227-233) */
+  double sigma[10];             /* the ten leading singular values */
+  double t_read, t_gram, t_iter, t_project, t_write;   /* seconds: reader, Gram + centring, iteration, projection, writers */
+} fq_svd_result_t;
+void fq_svd_default_opts(fq_svd_opts_t *o);
+int fq_svd_create(const fq_svd_opts_t *o, fq_svd_t **out);
+/* SVDcalculator::ReadVcf (:18-193): plain, gzip or BGZF text.  FQ_EINVAL with fq_svd_last_error for what the reference ends on (a duplicated marker, a negative PL,
+ * no GT / GL / PL key, no samples), for where it indexes out of bounds (a GT with one allele, fewer than three PL / GL values; the line is named) and for fewer
+ * than ten kept markers or ten samples (WriteSVD prints ten columns unconditionally, :263-272). */
+int fq_svd_read_vcf(fq_svd_t *p, const char *path);
+/* the panel from memory instead: g[n_marker][n_sample] in -1 .. 2 (ReadVcf's perMarkerGeno); chrom / pos / ref / alt per marker and the sample names may be
+ * NULL (chromosome "1", positions 1 .., A > C, S0 ..) */
+int fq_svd_set_genotypes(fq_svd_t *p, const int8_t *g, int32_t n_marker, int32_t n_sample, const char *const *chrom, const int32_t *pos, const char *ref, const char *alt,
+                         const char *const *samples);
+int fq_svd_gram(fq_svd_t *p, int32_t *out);                      /* (tests) G^T G, n_sample x n_sample */
+int fq_svd_run(fq_svd_t *p);                                     /* replaces the JacobiSVD call and the products behind it (:211-233) */
+int fq_svd_result(const fq_svd_t *p, fq_svd_result_t *out);      /* (the pointers hold until the next call that changes the object) */
+int fq_svd_write(fq_svd_t *p, const char *prefix);               /* WriteSVD (:248-279): prefix.mu, .UD, .V, .bed */
+const char *fq_svd_last_error(const fq_svd_t *p);                /* (NULL p: the error of a failed fq_svd_create on this thread) */
+void fq_svd_destroy(fq_svd_t *p);
+
 #ifdef __cplusplus
 }
 #endif
