@@ -139,7 +139,13 @@ class PopconResult(C.Structure):      # fq_popcon_result_t
 
 
 class SvdOpts(C.Structure):      # fq_svd_opts_t
-    _fields_ = [("host_eval", C.c_int32), ("device", C.c_int32), ("host_threads", C.c_int32), ("max_iter", C.c_int32), ("tol", C.c_double)]
+    _fields_ = [("host_eval", C.c_int32), ("device", C.c_int32), ("host_threads", C.c_int32), ("max_iter", C.c_int32), ("tol", C.c_double),
+                ("reader", C.c_int32), ("chunk_bytes", C.c_int64)]
+
+
+class SvdReadStats(C.Structure):      # fq_svd_read_stats_t
+    _fields_ = [("lines", C.c_int64), ("site_lines", C.c_int64), ("kept", C.c_int64), ("host_lines", C.c_int64), ("chunks", C.c_int64), ("members", C.c_int64), ("members_host", C.c_int64),
+                ("sites", C.c_int64), ("sites_found", C.c_int64), ("t_inflate", C.c_double), ("t_lines", C.c_double), ("t_site", C.c_double), ("t_geno", C.c_double), ("t_host", C.c_double)]
 
 
 class SvdResult(C.Structure):      # fq_svd_result_t
@@ -163,7 +169,8 @@ EXPORTS = ["fq_default_opts", "fq_index_build", "fq_index_load", "fq_index_destr
            "fq_bam_create_sorted", "fq_bam_sort_stats", "fq_bam_sort_stats_at_close", "fq_bam_sort_run_entries", "fq_sort_keys_device",
            "fq_popcon_default_opts", "fq_popcon_create", "fq_popcon_set_pileup_file", "fq_popcon_set_pileup_arrays", "fq_popcon_llk", "fq_popcon_marker_llk", "fq_popcon_run", "fq_popcon_result",
            "fq_popcon_write", "fq_popcon_last_error", "fq_popcon_destroy", "fq_popcon_marker_index", "fq_popcon_marker_alleles", "fq_qc_piles",
-           "fq_svd_default_opts", "fq_svd_create", "fq_svd_read_vcf", "fq_svd_set_genotypes", "fq_svd_gram", "fq_svd_run", "fq_svd_result", "fq_svd_write", "fq_svd_last_error", "fq_svd_destroy"]
+           "fq_svd_default_opts", "fq_svd_create", "fq_svd_read_vcf", "fq_svd_set_genotypes", "fq_svd_gram", "fq_svd_run", "fq_svd_result", "fq_svd_write", "fq_svd_last_error", "fq_svd_destroy",
+           "fq_svd_read_panel", "fq_svd_read_stats", "fq_svd_panel"]
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)
 EMIT_SAM = 1
 
@@ -328,6 +335,10 @@ def load_library(path: str | None = None):
         L.fq_svd_last_error.restype = C.c_char_p
         L.fq_svd_destroy.argtypes = [C.c_void_p]
         L.fq_svd_destroy.restype = None
+    if hasattr(L, "fq_svd_read_panel"):
+        L.fq_svd_read_panel.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_int32, C.c_char_p]
+        L.fq_svd_read_stats.argtypes = [C.c_void_p, C.POINTER(SvdReadStats)]
+        L.fq_svd_panel.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]
     return L
 
 
@@ -1252,11 +1263,17 @@ class Svd:
     """The SVD files of a reference panel (fq_svd_*): what `FASTQuick pop+con --RefVCF` (VerifyBamID2's SVDcalculator) makes.  The Gram matrix, the iteration's
     step and the projection run in the kernels of csrc/fq_svd.h on `device`, or -- host_eval -- as host loops over the same statements."""
 
-    def __init__(self, host_eval: bool = False, device: int = 0, host_threads: int = 0, max_iter: int | None = None, tol: float | None = None, lib=None):
+    READERS = {"serial": 0, "device": 1, "host_loops": 2}
+
+    def __init__(self, host_eval: bool = False, device: int = 0, host_threads: int = 0, max_iter: int | None = None, tol: float | None = None, lib=None,
+                 reader: int | str = 0, chunk_bytes: int | None = None):
         self.L = lib or load_library()
         o = SvdOpts()
         self.L.fq_svd_default_opts(C.byref(o))
         o.host_eval, o.device, o.host_threads = int(host_eval), device, host_threads
+        o.reader = self.READERS[reader] if isinstance(reader, str) else int(reader)
+        if chunk_bytes is not None:
+            o.chunk_bytes = chunk_bytes
         if max_iter is not None:
             o.max_iter = max_iter
         if tol is not None:
@@ -1277,6 +1294,36 @@ class Svd:
         self.L.fq_svd_result(self.h, C.byref(r))
         self.n_sample = r.n_sample
         return r.n_marker, r.n_sample
+
+    def read_panel(self, paths, sites: str | None = None):
+        """the panel from one VCF or a list of them read as one stream, optionally cut down to the sites of a file, by the reader chosen at creation"""
+        if isinstance(paths, (str, bytes)):
+            paths = [paths]
+        arr = (C.c_char_p * len(paths))(*[os.fsencode(x) for x in paths])
+        self._check(self.L.fq_svd_read_panel(self.h, arr, len(paths), os.fsencode(sites) if sites is not None else None), "fq_svd_read_panel")
+        r = SvdResult()
+        self.L.fq_svd_result(self.h, C.byref(r))
+        self.n_sample = r.n_sample
+        return r.n_marker, r.n_sample
+
+    def read_stats(self):
+        st = SvdReadStats()
+        self._check(self.L.fq_svd_read_stats(self.h, C.byref(st)), "fq_svd_read_stats")
+        out = {k: getattr(st, k) for k, _ in SvdReadStats._fields_ if not k.startswith("t_")}
+        out["seconds"] = {"inflate": st.t_inflate, "lines": st.t_lines, "site": st.t_site, "geno": st.t_geno, "host": st.t_host}
+        return out
+
+    def panel(self):
+        """what the reader kept: genotypes (markers x samples, int8), chrom and pos per marker, the sample names"""
+        r = SvdResult()
+        self.L.fq_svd_result(self.h, C.byref(r))
+        M, N = r.n_marker, r.n_sample
+        g = np.zeros((M, N), dtype=np.int8)
+        pos = np.zeros(M, dtype=np.int32)
+        chrom = (C.c_char_p * max(M, 1))()
+        names = (C.c_char_p * max(N, 1))()
+        self._check(self.L.fq_svd_panel(self.h, g.ctypes.data, pos.ctypes.data, chrom, names), "fq_svd_panel")
+        return {"g": g, "pos": pos, "chrom": [chrom[i].decode() for i in range(M)], "samples": [names[j].decode() for j in range(N)]}
 
     def set_genotypes(self, G, sites=None, samples=None):
         """G: markers x samples in -1 .. 2; sites: (chrom, pos, ref, alt) per marker; samples: the names"""

@@ -25,6 +25,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <fstream>
 #include <vector>
 
 #include "../../include/fastquick_amd.h"
@@ -45,6 +46,8 @@
 #pragma weak fq_svd_default_opts
 #pragma weak fq_svd_create
 #pragma weak fq_svd_read_vcf
+#pragma weak fq_svd_read_panel
+#pragma weak fq_svd_read_stats
 #pragma weak fq_svd_run
 #pragma weak fq_svd_result
 #pragma weak fq_svd_write
@@ -149,7 +152,7 @@ int usage() {
                   "       FASTQuick_amd index --ref REDUCED.FASTQuick.fa [--rollhash]\n"
                   "       FASTQuick_amd pop+con --PileupFile F --SVDPrefix P | --UDPath U --MeanPath M --BedPath B  --Output O [--NumPC INT] [--WithinAncestry] [--FixPC a:b:..] [--FixAlpha FLOAT] [--KnownAF F]\n"
                   "                       [--DisableSanityCheck] [--Epsilon FLOAT] [--host_eval] [--device INT]\n"
-                  "       FASTQuick_amd svd --RefVCF PANEL.vcf[.gz] [--Output P] [--host_eval] [--device INT]\n");
+                  "       FASTQuick_amd svd --RefVCF PANEL.vcf[.gz] | --RefVCFList LIST  [--Sites SITES.vcf] [--Output P] [--reader serial|device|host_loops] [--chunk_bytes INT] [--host_eval] [--device INT]\n");
   return 1;
 }
 
@@ -1173,31 +1176,71 @@ static int svd_main(int argc, char **argv) {
   if (!fq_svd_create) die("svd: this build of the library has no SVD calculator");
   fq_svd_opts_t o;
   fq_svd_default_opts(&o);
-  std::string vcf, out;
+  std::string vcf, list, sites, out, reader;
   for (int i = 2; i < argc; ++i) {
     const std::string f = argv[i];
     auto need = [&]() -> const char * { if (i + 1 >= argc) die("missing value for " + f); return argv[++i]; };
     if (f == "--RefVCF") vcf = need();
+    else if (f == "--RefVCFList") list = need();
+    else if (f == "--Sites") sites = need();
+    else if (f == "--reader") reader = need();
+    else if (f == "--chunk_bytes") o.chunk_bytes = atoll(need());
     else if (f == "--Output") out = need();
     else if (f == "--host_eval") o.host_eval = 1;
     else if (f == "--device") o.device = atoi(need());
     else die("unknown option " + f);
   }
-  if (vcf.empty()) die("svd: --RefVCF is required");
+  if (vcf.empty() && list.empty()) die("svd: --RefVCF is required (or --RefVCFList)");
+  if (!vcf.empty() && !list.empty()) die("svd: --RefVCF and --RefVCFList exclude each other");
+  // the reader: the serial one for a single VCF unless --reader says otherwise; a list or --Sites is the chunked reader's
+  const bool chunked_input = !list.empty() || !sites.empty();
+  if (reader.empty()) o.reader = chunked_input ? (o.host_eval ? 2 : 1) : 0;
+  else if (reader == "serial") o.reader = 0;
+  else if (reader == "device") o.reader = 1;
+  else if (reader == "host_loops") o.reader = 2;
+  else die("svd: --reader is serial, device or host_loops");
+  if (o.reader == 0 && chunked_input) die("svd: --reader serial reads one --RefVCF: --RefVCFList and --Sites need the device or host_loops reader");
+  if (o.chunk_bytes < 0) die("svd: --chunk_bytes must be positive");
+  if (o.reader != 0 && !fq_svd_read_panel) die("svd: this build of the library has no chunked reader");
+  std::vector<std::string> files;
+  if (!list.empty()) {
+    if (out.empty()) die("svd: --RefVCFList needs --Output");
+    std::ifstream lf(list);
+    if (!lf) die("svd: cannot open " + list);
+    for (std::string ln; std::getline(lf, ln);) {
+      while (!ln.empty() && (ln.back() == '\r' || ln.back() == ' ' || ln.back() == '\t')) ln.pop_back();
+      if (!ln.empty()) files.push_back(ln);
+    }
+    if (files.empty()) die("svd: " + list + " names no file");
+  } else files.push_back(vcf);
   if (out.empty()) out = vcf;
-  if (!o.host_eval) fq_runtime_configure(0, 1);
+  if (!o.host_eval || o.reader == 1) fq_runtime_configure(0, 1);
   fq_svd_t *p = nullptr;
   if (fq_svd_create(&o, &p)) die(fq_svd_last_error(nullptr));
   auto fail = [&](const char *what) { const std::string m = std::string(what) + ": " + fq_svd_last_error(p); fq_svd_destroy(p); die(m); };
-  if (fq_svd_read_vcf(p, vcf.c_str())) fail("svd");
+  std::string read_note = "serial reader";
+  if (o.reader == 0) { if (fq_svd_read_vcf(p, vcf.c_str())) fail("svd"); }
+  else {
+    std::vector<const char *> cp;
+    for (const auto &x : files) cp.push_back(x.c_str());
+    if (fq_svd_read_panel(p, cp.data(), (int32_t)cp.size(), sites.empty() ? nullptr : sites.c_str())) fail("svd");
+    fq_svd_read_stats_t rs;
+    fq_svd_read_stats(p, &rs);
+    if (!sites.empty()) fprintf(stderr, "NOTICE - Sites: %lld given, %lld found in the panel, %lld not found\n", (long long)rs.sites, (long long)rs.sites_found, (long long)(rs.sites - rs.sites_found));
+    char note[400];
+    snprintf(note, sizeof note, "%s reader: %lld lines, %lld at sites, %lld on the host, %lld chunks, %lld members; inflate %.3f s, line index %.3f s, site %.3f s, genotype %.3f s, host %.3f s",
+             o.reader == 1 ? "device" : "host_loops", (long long)rs.lines, (long long)rs.site_lines, (long long)rs.host_lines, (long long)rs.chunks, (long long)(rs.members + rs.members_host), rs.t_inflate,
+             rs.t_lines, rs.t_site, rs.t_geno, rs.t_host);
+    read_note = note;
+  }
   fq_svd_result_t r;
   fq_svd_result(p, &r);
   fprintf(stderr, "NOTICE - Number of Markers:%d\nNOTICE - Number of Individuals:%d\n", r.n_marker, r.n_sample);
   if (fq_svd_run(p)) fail("svd");
   if (fq_svd_write(p, out.c_str())) fail("output");
   fq_svd_result(p, &r);
-  fprintf(stderr, "NOTICE - sigma_0 %g, %d iterations, residual %.3g (%s); read %.3f s, Gram %.3f s, iteration %.3f s, projection %.3f s, write %.3f s\n", r.sigma[0], r.iterations, r.residual,
-          o.host_eval ? "host loops" : "device kernels", r.t_read, r.t_gram, r.t_iter, r.t_project, r.t_write);
+  fprintf(stderr, "NOTICE - sigma_0 %g, %d iterations, residual %.3g (%s); read %.3f s, Gram %.3f s, iteration %.3f s, projection %.3f s, write %.3f s; %s\n", r.sigma[0], r.iterations, r.residual,
+          o.host_eval ? "host loops" : "device kernels", r.t_read, r.t_gram, r.t_iter, r.t_project, r.t_write, read_note.c_str());
   fq_svd_destroy(p);
   fprintf(stderr, "NOTICE - Success!\n");
   return 0;

@@ -22,6 +22,8 @@
 #include "fq_popcon.h"
 #define FQ_SVD_KERNELS
 #include "fq_svd.h"
+#define FQ_VCF_KERNELS
+#include "fq_vcf.h"
 
 namespace fqdev {
 
@@ -2198,6 +2200,29 @@ int svd_project(SvdDev *d, const double *v, double *ud) {
   FQ_HIP(hipGetLastError());
   if (d2h(ud, d->ud, (size_t)d->m * FQ_SVD_NPC * 8)) return -3;
   return sync();
+}
+
+// ---- svd: the chunked panel reader (fq_vcf.h) ----
+int launch_vcf_site(const FqVcfSiteArgs &a) {
+  FQ_PRE();
+  if (!a.n_lines) return 0;
+  hipLaunchKernelGGL(k_vcf_site, dim3(nblk((uint64_t)a.n_lines, 256)), dim3(256), 0, g_stream, a);
+  FQ_HIP(hipGetLastError());
+  return 0;
+}
+int launch_vcf_compact(const uint32_t *keep, const uint64_t *off, uint32_t *kept, uint32_t n) {
+  FQ_PRE();
+  if (!n) return 0;
+  hipLaunchKernelGGL(k_vcf_compact, dim3(nblk((uint64_t)n, 256)), dim3(256), 0, g_stream, keep, off, kept, n);
+  FQ_HIP(hipGetLastError());
+  return 0;
+}
+int launch_vcf_geno(const FqVcfGenoArgs &a) {
+  FQ_PRE();
+  if (!a.n_kept) return 0;
+  hipLaunchKernelGGL(k_vcf_geno, dim3(a.n_kept), dim3(256), 0, g_stream, a);
+  FQ_HIP(hipGetLastError());
+  return 0;
 }
 
 // dynamic-LDS limits of the kernels that ask for more than the default 64 KB: once per device (state_create)

@@ -1,6 +1,6 @@
 // fq_svd.cpp -- `FASTQuick pop+con --RefVCF` (VerifyBamID2's SVDcalculator) around the statements of fq_svd.h: the subcommand `svd`.
 //
-// Host side: the VCF reader (SVDcalculator::ReadVcf, SVDcalculator.cpp:18-193, with libVcf's tokenising of a record: libVcfFile.cpp:473-530, :910-940,
+// Host side: the serial VCF reader (its statement for one record stands in fq_svd_host.h, shared with the chunked reader of fq_vcf.cpp; SVDcalculator::ReadVcf, SVDcalculator.cpp:18-193, with libVcf's tokenising of a record: libVcfFile.cpp:473-530, :910-940,
 // and String::AsInteger, StringBasics.cpp:1015-1068), the block subspace iteration with its orthonormalisation and Rayleigh-Ritz step, the sign rule
 // and the writers (WriteSVD, SVDcalculator.cpp:248-279).  The five statements of fq_svd.h run in its kernels (fq_device.hip: svd_gram, svd_apply,
 // svd_project) or -- opts.host_eval -- as host loops over the same int8 matrix: the CPU tier.
@@ -21,32 +21,7 @@
 #include "fastquick_amd.h"
 #include "fq_backend.h"
 #include "fq_svd.h"
-
-struct fq_svd {
-  fq_svd_opts_t o{};
-  std::string err;
-  // the panel: genotypes markers x samples as ReadVcf keeps them, the kept markers' sites, chooseBed
-  int32_t M = 0, N = 0;
-  std::vector<int8_t> g;
-  std::vector<std::string> samples, chrom;
-  std::vector<int32_t> pos;
-  std::unordered_map<std::string, std::unordered_map<int32_t, std::pair<char, char>>> bed;
-  // the decomposition
-  std::vector<double> mu, ud, v, sigma;
-  int32_t iterations = 0;
-  double residual = 0, lambda0 = 0;
-  double t_read = 0, t_gram = 0, t_iter = 0, t_project = 0, t_write = 0;
-  bool ran = false;
-  // the sample-major padded matrix of fq_svd.h, and the device
-  int32_t n_pad = 0;
-  int64_t m_pad = 0;
-  std::vector<int8_t> gt;
-  std::vector<double> c;      // host_eval: the centred Gram matrix
-  fqdev::State *dev = nullptr;
-  fqdev::SvdDev *dd = nullptr;
-
-  int fail(int rc, const std::string &m) { err = m; return rc; }
-};
+#include "fq_svd_host.h"
 
 namespace {
 
@@ -67,55 +42,7 @@ void parallel_for(int64_t n, int nt, const std::function<void(int64_t, int64_t)>
   for (auto &t : th) t.join();
 }
 
-// String::AsInteger: an optional '-', an optional 0x, digits up to the first character that is none
-long as_integer(const char *s, size_t len) {
-  long v = 0;
-  int base = 10;
-  size_t i = 0;
-  long sign = 1;
-  if (i == len) return 0;
-  if (s[i] == '-') { sign = -1; ++i; }
-  if (len > i + 2 && s[i] == '0' && (s[i + 1] == 'x' || s[i + 1] == 'X')) { base = 16; i += 2; }
-  for (; i < len; ++i) {
-    const int d = s[i] >= 'a' && s[i] <= 'z' ? s[i] - 32 : s[i];
-    if (d >= '0' && d <= '9') v = (long)((unsigned long)v * base + (unsigned long)(d - '0'));
-    else if (d >= 'A' && d <= 'F' && base == 16) v = (long)((unsigned long)v * base + (unsigned long)(d - 'A' + 10));
-    else break;
-  }
-  return sign * v;
-}
-struct Span { const char *p; size_t n; };
-// StringArray::ReplaceColumns: every separator ends a column, empty ones included
-void columns(const char *p, size_t n, char sep, std::vector<Span> &out) {
-  out.clear();
-  size_t a = 0;
-  for (size_t i = 0; i <= n; ++i)
-    if (i == n || p[i] == sep) { out.push_back({p + a, i - a}); a = i + 1; }
-}
-// StringArray::ReplaceTokens: runs of separators are skipped, no empty token
-void tokens(const char *p, size_t n, const char *seps, std::vector<Span> &out) {
-  out.clear();
-  size_t i = 0;
-  while (i < n) {
-    while (i < n && strchr(seps, p[i])) ++i;
-    const size_t a = i;
-    while (i < n && !strchr(seps, p[i])) ++i;
-    if (a < n) out.push_back({p + a, i - a});
-  }
-}
-bool is(const Span &s, const char *lit) { return s.n == strlen(lit) && !memcmp(s.p, lit, s.n); }
-int find_key(const std::vector<Span> &keys, const char *k) {
-  for (size_t i = 0; i < keys.size(); ++i) if (is(keys[i], k)) return (int)i;
-  return -1;
-}
-bool accept_chrom(const std::string &c) {   // acceptChr: 1 .. 22, chr1 .. chr22
-  const char *s = c.c_str();
-  if (!strncmp(s, "chr", 3)) s += 3;
-  const size_t n = strlen(s);
-  if (n < 1 || n > 2 || s[0] < '1' || s[0] > '9' || (n == 2 && (s[1] < '0' || s[1] > '9'))) return false;
-  const int v = atoi(s);
-  return v >= 1 && v <= 22;
-}
+using namespace fqsvd;
 
 void clear_panel(fq_svd *p) {
   if (p->dd) { if (p->dev && !fqdev::bind(p->dev)) fqdev::svd_free(p->dd); p->dd = nullptr; }
@@ -123,6 +50,7 @@ void clear_panel(fq_svd *p) {
   p->g.clear(); p->samples.clear(); p->chrom.clear(); p->pos.clear(); p->bed.clear();
   p->gt.clear(); p->c.clear();
   p->ran = false;
+  p->rs = fq_svd_read_stats_t{};
 }
 
 int read_text(fq_svd *p, const char *path, std::string &text) {   // plain, gzip or BGZF: zlib reads all three
@@ -144,14 +72,11 @@ int read_text(fq_svd *p, const char *path, std::string &text) {   // plain, gzip
 int read_vcf(fq_svd *p, const char *path) {
   std::string text;
   if (int rc = read_text(p, path, text)) return rc;
-  const int maxPhred = 255;
   bool have_header = false;
-  std::string prev_name, name;
-  std::vector<Span> tok, keys, cell, val;
-  std::vector<int8_t> row;
+  RecState S;
+  S.path = path;
+  int64_t &line_no = S.line_no;
   size_t at = 0;
-  int64_t line_no = 0;
-  auto where = [&]() { return " (line " + std::to_string(line_no) + " of " + path + ")"; };
   while (at < text.size()) {
     size_t e = text.find('\n', at);
     if (e == std::string::npos) e = text.size();
@@ -163,92 +88,16 @@ int read_vcf(fq_svd *p, const char *path) {
     if (!have_header) {
       if (n >= 2 && ln[0] == '#' && ln[1] == '#') continue;
       if (n >= 2 && ln[0] == '#' && ln[1] == 'C') {
-        columns(ln, n, '\t', tok);
-        for (size_t i = 9; i < tok.size(); ++i) p->samples.emplace_back(tok[i].p, tok[i].n);
+        header_samples(ln, n, p->samples);
         have_header = true;
         if (p->samples.empty()) return p->fail(FQ_EINVAL, std::string("No individual genotype information exist in the input VCF file ") + path);
         p->N = (int32_t)p->samples.size();
-        row.assign(p->N, -1);
         continue;
       }
-      return p->fail(FQ_EINVAL, "Header line is not found : #CHROM..." + where());
+      return p->fail(FQ_EINVAL, "Header line is not found : #CHROM..." + S.where());
     }
     if (n == 0) break;   // (the reference's reader ends at an empty line)
-    columns(ln, n, '\t', tok);
-    if (tok.size() < 5) return p->fail(FQ_EINVAL, "a record with fewer than five columns" + where());
-    const std::string chrom(tok[0].p, tok[0].n);
-    const int32_t pos = atoi(std::string(tok[1].p, tok[1].n).c_str());
-    name = chrom + ":" + std::to_string(pos);
-    if (prev_name == name) return p->fail(FQ_EINVAL, "Duplicated Marker at " + name + where());
-    if (!accept_chrom(chrom)) continue;
-    size_t alt_len = 0;
-    while (alt_len < tok[4].n && tok[4].p[alt_len] != ',') ++alt_len;   // of several ALT alleles the first
-    if (tok[3].n > 1 || alt_len > 1) continue;
-    if (tok[3].n == 0 || alt_len == 0) return p->fail(FQ_EINVAL, "an empty REF or ALT allele" + where());
-    if (tok.size() < 10) return p->fail(FQ_EINVAL, "a record without FORMAT and genotype columns" + where());
-    const char ref = (char)toupper((unsigned char)tok[3].p[0]), alt = (char)toupper((unsigned char)tok[4].p[0]);
-    columns(tok[8].p, tok[8].n, ':', keys);
-    int idx = find_key(keys, "PL"), flag = 0;   // 0 for PL, 1 for GL, 2 for GT
-    if (idx < 0) {
-      idx = find_key(keys, "GL");
-      if (idx >= 0) flag = 1;
-      else {
-        idx = find_key(keys, "GT");
-        if (idx >= 0) flag = 2;
-        else return p->fail(FQ_EINVAL, "Cannot recognize GT, GL or PL key in FORMAT field" + where());
-      }
-    }
-    const size_t first = (tok[9].n == 0 && tok.size() > 10) ? 10 : 9;   // (libVcf steps over an empty column behind FORMAT)
-    if (tok.size() - first != (size_t)p->N) return p->fail(FQ_EINVAL, "a record with " + std::to_string(tok.size() - first) + " genotype columns under " + std::to_string(p->N) + " sample names" + where());
-    for (int32_t i = 0; i < p->N; ++i) {
-      const Span &sv = tok[first + i];
-      Span value;
-      if (is(sv, "./.") || is(sv, ".")) value = idx == 0 ? Span{"./.", 3} : Span{"", 0};   // (libVcf: the first value "./.", the others empty)
-      else {
-        columns(sv.p, sv.n, ':', cell);
-        if (cell.size() != keys.size()) return p->fail(FQ_EINVAL, "# values = " + std::string(sv.p, sv.n) + " do not match with # fields in FORMAT field = " + std::to_string(keys.size()) + " at sampleIndex = " + std::to_string(i) + where());
-        value = cell[idx];
-      }
-      long phred11, phred12, phred22;
-      if (flag == 2) {
-        tokens(value.p, value.n, "|/", val);
-        if (val.size() < 2) return p->fail(FQ_EINVAL, "a GT with fewer than two alleles: '" + std::string(value.p, value.n) + "', sample " + std::to_string(i) + where());
-        const long geno = as_integer(val[0].p, val[0].n) + as_integer(val[1].p, val[1].n);
-        if (geno == 0) { phred11 = 0; phred12 = 30; phred22 = 50; }
-        else if (geno == 1) { phred11 = 50; phred12 = 0; phred22 = 50; }
-        else { phred11 = 50; phred12 = 30; phred22 = 0; }
-      } else {
-        tokens(value.p, value.n, ",", val);
-        if (val.size() < 3) return p->fail(FQ_EINVAL, std::string("a ") + (flag ? "GL" : "PL") + " with fewer than three values: '" + std::string(value.p, value.n) + "', sample " + std::to_string(i) + where());
-        long ph[3];
-        for (int k = 0; k < 3; ++k) {
-          if (flag == 0) ph[k] = as_integer(val[k].p, val[k].n);
-          else {
-            const double x = -10. * atof(std::string(val[k].p, val[k].n).c_str());
-            if (!(x > -2147483648. && x < 2147483648.)) return p->fail(FQ_EINVAL, "a GL beyond what an int holds" + where());
-            ph[k] = static_cast<int>(x);
-          }
-        }
-        phred11 = ph[0]; phred12 = ph[1]; phred22 = ph[2];
-      }
-      if (phred11 < 0 || phred12 < 0 || phred22 < 0) return p->fail(FQ_EINVAL, "Negative PL or Positive GL observed" + where());
-      if (phred11 > maxPhred) phred11 = maxPhred;
-      if (phred12 > maxPhred) phred12 = maxPhred;
-      if (phred22 > maxPhred) phred22 = maxPhred;
-      int minGeno = -1;
-      long minPhred = maxPhred;
-      if (phred11 < minPhred) { minPhred = phred11; minGeno = 0; }
-      if (phred12 < minPhred) { minPhred = phred12; minGeno = 1; }
-      if (phred22 < minPhred) { minPhred = phred22; minGeno = 2; }
-      row[i] = (int8_t)minGeno;
-    }
-    if (p->M == FQ_SVD_MAX_MARKERS) return p->fail(FQ_ELIMIT, "svd: more than 2^29 markers");
-    p->bed[chrom][pos] = std::make_pair(ref, alt);
-    p->chrom.push_back(chrom);
-    p->pos.push_back(pos);
-    p->g.insert(p->g.end(), row.begin(), row.end());
-    p->M++;
-    prev_name = name;
+    if (const int rc = fq_svd_record(p, S, ln, n); rc < 0) return rc;
   }
   if (!have_header) return p->fail(FQ_EINVAL, std::string("Header line is not found : #CHROM... (") + path + ")");
   return 0;
@@ -450,6 +299,7 @@ void fq_svd_default_opts(fq_svd_opts_t *o) {
   memset(o, 0, sizeof *o);
   o->max_iter = 2000;
   o->tol = 1e-11;
+  o->chunk_bytes = (int64_t)256 << 20;
 }
 
 int fq_svd_create(const fq_svd_opts_t *o, fq_svd_t **out) {
@@ -460,6 +310,8 @@ int fq_svd_create(const fq_svd_opts_t *o, fq_svd_t **out) {
   fq_svd_default_opts(&d);
   if (o) d = *o;
   if (d.max_iter < 1 || !(d.tol > 0)) { g_create_err = "svd: max_iter must be at least 1 and tol positive"; return FQ_EINVAL; }
+  if (d.reader < 0 || d.reader > 2 || d.chunk_bytes < 0) { g_create_err = "svd: reader is 0 (serial), 1 (kernels) or 2 (host loops), chunk_bytes not negative"; return FQ_EINVAL; }
+  if (!d.chunk_bytes) d.chunk_bytes = (int64_t)256 << 20;
   fq_svd *p = new fq_svd;
   p->o = d;
   *out = p;
@@ -587,6 +439,20 @@ int fq_svd_write(fq_svd_t *p, const char *prefix) {
   fBed.close(); fMu.close(); fUD.close(); fPC.close();
   if (!fBed || !fMu || !fUD || !fPC) return p->fail(FQ_EIO, "Errors detected when writing to " + Prefix + ".{mu,UD,V,bed} !");
   p->t_write = now() - t0;
+  return 0;
+}
+
+int fq_svd_read_stats(const fq_svd_t *p, fq_svd_read_stats_t *out) {
+  if (!p || !out) return FQ_EINVAL;
+  *out = p->rs;
+  return 0;
+}
+
+int fq_svd_panel(const fq_svd_t *p, int8_t *g, int32_t *pos, const char **chrom, const char **samples) {
+  if (!p) return FQ_EINVAL;
+  if (g && !p->g.empty()) memcpy(g, p->g.data(), p->g.size());
+  for (int32_t i = 0; i < p->M; ++i) { if (pos) pos[i] = p->pos[i]; if (chrom) chrom[i] = p->chrom[i].c_str(); }
+  for (int32_t j = 0; j < p->N; ++j) if (samples) samples[j] = p->samples[j].c_str();
   return 0;
 }
 

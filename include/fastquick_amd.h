@@ -741,6 +741,9 @@ typedef struct {
   int32_t host_threads;         /* threads of the host loops (0: fq_host_cpus(), at most 16) */
   int32_t max_iter;             /* cap of the iteration (2000): beyond it fq_svd_run is FQ_ELIMIT and nothing can be written */
   double tol;                   /* the iteration stops when max over c < 10 of |C q_c - lambda_c q_c| <= tol * lambda_0 (1e-11) */
+  int32_t reader;               /* fq_svd_read_panel: 0 the serial reader (fq_svd_read_vcf's), 1 the chunked reader as kernels (csrc/fq_vcf.h), 2 the same as host loops (no device
+                                   is opened, every form of input is inflated on the host) */
+  int64_t chunk_bytes;          /* text the chunked reader takes at a time (0: 256 MiB); a chunk grows to hold a whole line */
 } fq_svd_opts_t;
 typedef struct {
   int32_t n_marker, n_sample;   /* kept markers, samples */
@@ -762,6 +765,26 @@ int fq_svd_read_vcf(fq_svd_t *p, const char *path);
  * NULL (chromosome "1", positions 1 .., A > C, S0 ..) */
 int fq_svd_set_genotypes(fq_svd_t *p, const int8_t *g, int32_t n_marker, int32_t n_sample, const char *const *chrom, const int32_t *pos, const char *ref, const char *alt,
                          const char *const *samples);
+/* The panel from one or several VCFs read in order as one stream of records (`bcftools concat`), optionally cut down to the sites of a file (`bcftools view -v snps
+ * -R`; NULL: every record): opts.reader says by which reader.  Plain, gzip or BGZF text; BGZF members are inflated on the device under reader 1.  Every file's sample
+ * names must equal the first's.  sites: a VCF or any tab-separated text whose first two columns are CHROM and POS ('#' lines skipped; plain or gzip); a record is
+ * handed to the reader only if (a) its CHROM and POS equal a site's, a leading chr / CHR removed on both sides, and (b) REF is one base and some ALT allele is one base
+ * of ACGTacgt other than REF.  Errors, line numbers and kept markers are fq_svd_read_vcf's.  The serial reader takes one path and no sites. */
+int fq_svd_read_panel(fq_svd_t *p, const char *const *paths, int32_t n_paths, const char *sites_or_null);
+typedef struct {
+  int64_t lines;                /* record lines read (behind the headers) */
+  int64_t site_lines;           /* of those, the lines that passed the site test (= lines without sites) */
+  int64_t kept;                 /* kept markers */
+  int64_t host_lines;           /* lines the host's per-record statement parsed (needs_host) */
+  int64_t chunks, members;      /* chunks of text; BGZF members inflated by the kernel (members_host: by the host after the kernel refused them) */
+  int64_t members_host;
+  int64_t sites, sites_found;   /* sites given; sites at which a record was handed to the reader */
+  double t_inflate, t_lines, t_site, t_geno, t_host;   /* seconds: inflate (reading and uploads included), line index, site kernel + compaction, genotype kernel, host fallback + merge */
+} fq_svd_read_stats_t;
+int fq_svd_read_stats(const fq_svd_t *p, fq_svd_read_stats_t *out);   /* of the last fq_svd_read_panel (zeros after another reader) */
+/* what the reader kept: g[n_marker][n_sample], pos[n_marker], chrom[n_marker] and samples[n_sample] (pointers into the object, until the next call that changes it);
+ * any of them may be NULL.  The sizes are fq_svd_result's n_marker and n_sample. */
+int fq_svd_panel(const fq_svd_t *p, int8_t *g, int32_t *pos, const char **chrom, const char **samples);
 int fq_svd_gram(fq_svd_t *p, int32_t *out);                      /* (tests) G^T G, n_sample x n_sample */
 int fq_svd_run(fq_svd_t *p);                                     /* replaces the JacobiSVD call and the products behind it (:211-233) */
 int fq_svd_result(const fq_svd_t *p, fq_svd_result_t *out);      /* (the pointers hold until the next call that changes the object) */
