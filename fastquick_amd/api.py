@@ -86,7 +86,8 @@ class Stats(C.Structure):
                 ("wall_ms_total", C.c_double), ("wave_trips", C.c_uint64), ("lane_trips", C.c_uint64),
                 ("h2d_bytes", C.c_uint64), ("d2h_bytes", C.c_uint64), ("pairs_on_device", C.c_uint64), ("dbg", C.c_uint64 * 16),
                 ("width_occ_touches", C.c_uint64), ("md_reads", C.c_uint64), ("host_pairs", C.c_uint64),
-                ("device_wait_ms", C.c_double), ("host_cpu_ms", C.c_double), ("dp_launches", C.c_uint64 * 6)]
+                ("device_wait_ms", C.c_double), ("host_cpu_ms", C.c_double), ("dp_launches", C.c_uint64 * 6),
+                ("filter_binned_reads", C.c_uint64), ("filter_bin_spill", C.c_uint64)]
 
 
 class FrontEndStats(C.Structure):

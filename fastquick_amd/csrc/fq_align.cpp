@@ -474,6 +474,7 @@ extern "C" int fq_ctx_set_tuning(fq_ctx_t *c, const char *key, int64_t v) {
   else if (k == "gap_refill_min") t->gap_refill_min = (int)v;
   else if (k == "filter_no_turns") t->filter_no_turns = (int)v;
   else if (k == "prep_priority") t->prep_priority = (int)v;
+  else if (k == "filter_binned_min") t->filter_binned_min = std::max<int64_t>(0, v);
   else if (k == "refine_lanes") t->refine_lanes = (int)v;
   else if (k == "gap_generic_opts") t->gap_generic_opts = (int)v;
   else if (k == "sw_serial_reverse") t->sw_serial_reverse = (int)v;
@@ -881,7 +882,12 @@ int stage0_filter(Call &K, const FilterIn &in) {
     FqPrepPackedArgs a{};
     a.ix = c->ix->dev; a.o = c->ko; a.head = in.head; a.len = ragged ? in.len : nullptr; a.uniform_len = in.uniform_len; a.qual_last = in.qual_last; a.sub_whole = c->d_sub_max.p + n_sub;
     a.n_reads = n_in; a.filtered = c->d_filtered.p; a.sub_max = c->d_sub_max.p; a.n_pairs = n; a.batch_pairs = B; a.counters = c->d_counters.p;
-    CK(fqdev::launch_prep_packed(a));
+    const fqdev::Tune *tn = fqdev::tune(c->dev);
+    a.binned = c->ko.filter_thresh != 0 && !tn->filter_no_turns && (int64_t)n_in >= tn->filter_binned_min && n_in < FQ_BIN_MAX_READS;
+    const int rc = fqdev::launch_prep_packed(a);
+    c->stats.filter_binned_reads += fqdev::filter_binned_reads; c->stats.filter_bin_spill += fqdev::filter_bin_spill;   // (before any return, as dp_take)
+    fqdev::filter_binned_reads = fqdev::filter_bin_spill = 0;
+    CK(rc);
   }
   CK(fqdev::launch_compact(c->d_filtered.p, n, c->d_read_list.p, c->d_sidx.p, c->d_pair_list.p, c->d_counts.p));
   fqdev::time_end(FQ_K_PREP);

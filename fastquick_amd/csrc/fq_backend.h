@@ -23,6 +23,7 @@ struct Tune {   // experiment / test knobs (fq_ctx_set_tuning); the defaults are
   int gap_generic_opts = 0; // 1: never the kernels specialised for FASTQuick's own option block (FqOptsStock)
   int width_both_strands = 0; // 1: the width kernel with one thread per read walking both strands (round 3's); default: one thread per (read, strand), strands apart by XCD
   int prep_priority = 0;     // 1: the packed filter kernel on a stream of the highest priority
+  int64_t filter_binned_min = 2621440; // packed / text filter: reads per launch from which the binned form runs (0: always)
   int sw_serial_reverse = 0; // 1: the mate-rescue kernel's reverse pass as the serial statement on one lane (the wavefront form is the default)
 };
 int runtime_configure(int hw_queues, int blocking_waits);   // fq_runtime_configure: before the process's first HIP call
@@ -67,6 +68,9 @@ void time_collect(double ms[], uint64_t launches[], int n_ids);   // after sync(
 // launches of the DP kernels per variant (FQ_DP_*), counted by the launchers of a backend that has variants and taken by the calling
 // thread right behind each launch (fq_align.cpp: dp_take); a backend with one loop per DP leaves them alone
 inline thread_local uint64_t dp_launches[FQ_DP_COUNT] = {};
+// reads that launch_prep_packed filtered in the binned form, and entries of it that took a fallback route (none exists: the bucket offsets are
+// counted), taken by the calling thread in the same way
+inline thread_local uint64_t filter_binned_reads = 0, filter_bin_spill = 0;
 
 // launchers (asynchronous on the backend's stream unless stated)
 int launch_prep(const FqPrepArgs &a);

@@ -99,6 +99,7 @@ static int g_turn_held[64];
 // the devices the library opens, says so with fq_runtime_configure() before its first HIP call (the command line and bench.py do);
 // the library says once when more contexts are created on a device than the queues in effect can keep apart.
 static int g_ctx_count[64];
+static void bin_scratch_free(int dev);   // the binned filter's scratch of a device (launch_prep_packed)
 static hipStream_t g_prio_stream[64];   // the filter kernels' stream of the highest priority (tuning key prep_priority), one per device
 static bool g_queue_warned = false;
 static int g_rt_blocking_waits = 0;
@@ -175,7 +176,7 @@ void state_destroy(State *s) {
   {
     std::lock_guard<std::mutex> lk(g_dev_mu);
     if (g_prep_owner[s->device] == s) { g_prep_owner[s->device] = nullptr; g_prep_last[s->device] = nullptr; }
-    if (g_ctx_count[s->device] > 0) --g_ctx_count[s->device];
+    if (g_ctx_count[s->device] > 0 && --g_ctx_count[s->device] == 0) bin_scratch_free(s->device);   // (the device's last state: nothing of it is in flight)
   }
   for (auto &p : s->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
   for (auto e : s->free_events) (void)hipEventDestroy(e);
@@ -1207,12 +1208,196 @@ __global__ void __launch_bounds__(256) k_prep_packed(FqPrepPackedArgs a) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r < a.n_reads) fq_prep_packed_thread(a, r);
 }
+// ---- the binned form of the packed filter (fq_kernels.h: "the same filter, binned") -------------------------------------------------
+// Scratch of a device, shared by its contexts (their filter launches are chained: one runs at a time): the entries, and zero between
+// launches the per-bucket counts and the per-read hit masks.  Sized by the largest launch seen; a block that had to grow is kept until the
+// device's last context goes (hipFree waits for every stream of the device: never inside a call).
+struct BinScratch {
+  FqBinEntry *ent = nullptr; size_t ent_cap = 0;
+  uint32_t *mask = nullptr; size_t mask_cap = 0;
+  uint32_t *count = nullptr, *base = nullptr, *cursor = nullptr, *chunks = nullptr;   // [FQ_BIN_BUCKETS] (+ 1: base, chunks), by position
+  std::vector<void *> retired;
+};
+static BinScratch g_bin[64];
+static void bin_scratch_free(int dev) {   // g_dev_mu held, nothing of the device in flight
+  BinScratch &b = g_bin[dev];
+  for (void *p : b.retired) (void)hipFree(p);
+  if (b.ent) (void)hipFree(b.ent);
+  if (b.mask) (void)hipFree(b.mask);
+  if (b.count) (void)hipFree(b.count);
+  b = BinScratch();
+}
+static int bin_scratch_ensure(int dev, size_t n_ent, size_t n_reads, hipStream_t st) {   // g_dev_mu held
+  BinScratch &b = g_bin[dev];
+  if (!b.count) {
+    constexpr size_t n = 4 * (size_t)FQ_BIN_BUCKETS + 2;
+    FQ_HIP(hipMalloc((void **)&b.count, n * 4));
+    b.base = b.count + FQ_BIN_BUCKETS; b.cursor = b.base + FQ_BIN_BUCKETS + 1; b.chunks = b.cursor + FQ_BIN_BUCKETS;
+    FQ_HIP(hipMemsetAsync(b.count, 0, n * 4, st));
+  }
+  if (n_ent > b.ent_cap) {
+    if (b.ent) b.retired.push_back(b.ent);
+    b.ent = nullptr; b.ent_cap = 0;
+    const size_t want = n_ent + n_ent / 8;
+    FQ_HIP(hipMalloc((void **)&b.ent, want * sizeof(FqBinEntry)));
+    b.ent_cap = want;
+  }
+  if (n_reads > b.mask_cap) {   // (an earlier launch on another stream may still hold the old block: it leaves it zero and nobody looks again)
+    if (b.mask) b.retired.push_back(b.mask);
+    b.mask = nullptr; b.mask_cap = 0;
+    const size_t want = n_reads + n_reads / 8;
+    FQ_HIP(hipMalloc((void **)&b.mask, want * 4));
+    b.mask_cap = want;
+    FQ_HIP(hipMemsetAsync(b.mask, 0, want * 4, st));
+  }
+  return 0;
+}
+constexpr int kBinThreads = 1024, kBinTile = 2 * kBinThreads;        // bin: reads per tile
+constexpr int kBinProbeThreads = 512, kBinProbePer = 2, kBinChunk = kBinProbeThreads * kBinProbePer;   // probe: entries per chunk
+constexpr int kBinProbeWgPerXcd = 32;   // one workgroup per CU; the chunks in flight on an XCD: 32,768 entries, less than a bucket of the headline's launch (profiles/hbm_probe_bench.txt)
+__device__ inline void bin_kmers(const FqPrepPackedArgs &a, int r, uint64_t kmer[3]) {
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) kmer[ch] = a.head[(size_t)ch * (size_t)a.n_reads + (size_t)r];
+}
+__global__ void __launch_bounds__(kBinThreads) k_prep_bin_count(FqPrepPackedArgs a, uint32_t *__restrict__ count) {
+  __shared__ uint32_t h[FQ_BIN_BUCKETS];
+  for (int i = threadIdx.x; i < FQ_BIN_BUCKETS; i += kBinThreads) h[i] = 0;
+  __syncthreads();
+  const int front = fq_filter_front(a.o.filter_thresh);
+  for (int64_t r = (int64_t)blockIdx.x * kBinThreads + threadIdx.x; r < a.n_reads; r += (int64_t)gridDim.x * kBinThreads) {
+    uint64_t kmer[3];
+    bin_kmers(a, (int)r, kmer);
+#pragma unroll
+    for (int q = 0; q < 18; ++q) if (q < front) atomicAdd(&h[fq_bin_pos(q, fq_filter_key(kmer, q))], 1u);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < FQ_BIN_BUCKETS; i += kBinThreads) if (h[i]) atomicAdd(&count[i], h[i]);
+}
+// base[p]: first entry of the bucket at position p (base[FQ_BIN_BUCKETS]: all); cursor[p] = base[p]; chunks[p]: chunks of kBinChunk entries
+// in front of it; count[] zero again.  One workgroup.
+__global__ void __launch_bounds__(256) k_prep_bin_offsets(uint32_t *__restrict__ count, uint32_t *__restrict__ base, uint32_t *__restrict__ cursor, uint32_t *__restrict__ chunks) {
+  static_assert(FQ_BIN_BUCKETS == 6 * 256, "six buckets per thread");
+  __shared__ uint32_t se[256], sc[256];
+  const int t = threadIdx.x;
+  uint32_t c[6], e = 0, k = 0;
+  for (int j = 0; j < 6; ++j) { c[j] = count[6 * t + j]; count[6 * t + j] = 0; e += c[j]; k += (c[j] + kBinChunk - 1) / kBinChunk; }
+  se[t] = e; sc[t] = k;
+  __syncthreads();
+  for (int d = 1; d < 256; d <<= 1) {
+    const uint32_t ae = t >= d ? se[t - d] : 0, ac = t >= d ? sc[t - d] : 0;
+    __syncthreads();
+    se[t] += ae; sc[t] += ac;
+    __syncthreads();
+  }
+  e = se[t] - e; k = sc[t] - k;
+  for (int j = 0; j < 6; ++j) { base[6 * t + j] = e; cursor[6 * t + j] = e; chunks[6 * t + j] = k; e += c[j]; k += (c[j] + kBinChunk - 1) / kBinChunk; }
+  if (t == 255) { base[FQ_BIN_BUCKETS] = e; chunks[FQ_BIN_BUCKETS] = k; }
+}
+// A tile of kBinTile reads per step, one table at a time: counting sort of the table's entries by the key's top byte in LDS, one claim per
+// bucket that has entries (exact: k_prep_bin_count counted the same keys), then the sorted tile leaves as runs of consecutive entries.
+__global__ void __launch_bounds__(kBinThreads) k_prep_bin(FqPrepPackedArgs a, FqBinEntry *__restrict__ ent, uint32_t *__restrict__ cursor) {
+  constexpr int RPT = kBinTile / kBinThreads;
+  __shared__ FqBinEntry sorted[kBinTile * 3];
+  __shared__ uint32_t h[256], start[256], delta[256];
+  const int tid = threadIdx.x, front = fq_filter_front(a.o.filter_thresh);
+  const int n_tiles = (a.n_reads + kBinTile - 1) / kBinTile;
+  for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    uint64_t kmer[RPT][3];
+#pragma unroll
+    for (int i = 0; i < RPT; ++i) {
+      const int64_t r = (int64_t)tile * kBinTile + i * kBinThreads + tid;
+      if (r < a.n_reads) bin_kmers(a, (int)r, kmer[i]);
+    }
+    for (int t = 0; t < 6; ++t) {
+      if (tid < 256) h[tid] = 0;
+      __syncthreads();
+      uint32_t key[RPT][3], rank[RPT][3];
+#pragma unroll
+      for (int i = 0; i < RPT; ++i) {
+        const int64_t r = (int64_t)tile * kBinTile + i * kBinThreads + tid;
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          if (t + 6 * j < front && r < a.n_reads) { key[i][j] = fq_kmer_project(kmer[i][j], t); rank[i][j] = atomicAdd(&h[key[i][j] >> 24], 1u); }
+      }
+      __syncthreads();
+      if (tid < 256) start[tid] = h[tid];
+      __syncthreads();
+      for (int d = 1; d < 256; d <<= 1) {
+        const uint32_t add = (tid < 256 && tid >= d) ? start[tid - d] : 0;
+        __syncthreads();
+        if (tid < 256) start[tid] += add;
+        __syncthreads();
+      }
+      const uint32_t n_ent = start[255];
+      __syncthreads();
+      if (tid < 256) {
+        const uint32_t c = h[tid], s = start[tid] - c;
+        start[tid] = s;
+        if (c) delta[tid] = atomicAdd(&cursor[fq_bin_pos(t, (uint32_t)tid << 24)], c) - s;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int i = 0; i < RPT; ++i) {
+        const int64_t r = (int64_t)tile * kBinTile + i * kBinThreads + tid;
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          if (t + 6 * j < front && r < a.n_reads) sorted[start[key[i][j] >> 24] + rank[i][j]] = fq_bin_entry(key[i][j], (int)r, t + 6 * j);
+      }
+      __syncthreads();
+      for (uint32_t i = tid; i < n_ent; i += kBinThreads) { const FqBinEntry e = sorted[i]; ent[delta[e.key >> 24] + i] = e; }
+      __syncthreads();
+    }
+  }
+}
+// Persistent workgroups; those with blockIdx % 8 == x take the chunks of list x in order (a long bucket is many chunks: a skewed batch
+// runs as long as its entries), so the chunks in flight on an XCD belong to one or two neighbouring buckets.
+__global__ void __launch_bounds__(kBinProbeThreads) k_prep_bin_probe(FqDevIndex ix, const FqBinEntry *__restrict__ ent, const uint32_t *__restrict__ base,
+                                                                     const uint32_t *__restrict__ chunks, uint32_t *__restrict__ mask) {
+  const int x = blockIdx.x % FQ_BIN_XCDS;
+  const uint32_t per = gridDim.x / FQ_BIN_XCDS, c0 = chunks[x * FQ_BIN_PER_XCD], c1 = chunks[(x + 1) * FQ_BIN_PER_XCD];
+  for (uint32_t k = c0 + blockIdx.x / FQ_BIN_XCDS; k < c1; k += per) {
+    int lo = x * FQ_BIN_PER_XCD, hi = (x + 1) * FQ_BIN_PER_XCD;      // the last position whose chunks begin at or before k: the bucket that holds chunk k
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (chunks[mid] <= k) lo = mid; else hi = mid; }
+    const uint8_t *region = fq_bin_region(ix, lo);
+    const uint32_t first = base[lo] + (k - chunks[lo]) * kBinChunk, end = base[lo + 1];
+    FqBinEntry e[kBinProbePer]; uint32_t hit[kBinProbePer];
+#pragma unroll
+    for (int i = 0; i < kBinProbePer; ++i) {
+      const uint32_t at = first + i * kBinProbeThreads + threadIdx.x;
+      if (at < end) e[i] = ent[at]; else e[i].tag = ~0u;      // (no entry's tag is all ones: a probe index is below 18)
+    }
+#pragma unroll
+    for (int i = 0; i < kBinProbePer; ++i) hit[i] = e[i].tag != ~0u ? fq_bin_hit(region, e[i]) : 0;
+#pragma unroll
+    for (int i = 0; i < kBinProbePer; ++i) if (hit[i]) atomicOr(&mask[fq_bin_read(e[i])], fq_bin_mask_bit(e[i]));
+  }
+}
+__global__ void __launch_bounds__(256) k_prep_bin_verdict(FqPrepPackedArgs a, uint32_t *__restrict__ mask) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < a.n_reads) fq_prep_binned_verdict_thread(a, mask, r);
+}
+// the five launches on `st` between the two timing events, which are recorded on the stream in front of the first and behind the last (the stage begin
+// to end; every launch is a plain one); g_dev_mu held and the scratch ensured (the scratch is the device's)
+static int launch_prep_binned(const FqPrepPackedArgs &a, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+  const BinScratch &b = g_bin[g_cur->device];
+  FQ_HIP(hipEventRecord(e0, st));
+  hipLaunchKernelGGL(k_prep_bin_count, dim3(std::min<unsigned>(512, nblk((uint64_t)a.n_reads, kBinThreads))), dim3(kBinThreads), 0, st, a, b.count);
+  hipLaunchKernelGGL(k_prep_bin_offsets, dim3(1), dim3(256), 0, st, b.count, b.base, b.cursor, b.chunks);
+  hipLaunchKernelGGL(k_prep_bin, dim3(std::min<unsigned>(512, nblk((uint64_t)a.n_reads, kBinTile))), dim3(kBinThreads), 0, st, a, b.ent, b.cursor);
+  hipLaunchKernelGGL(k_prep_bin_probe, dim3(FQ_BIN_XCDS * kBinProbeWgPerXcd), dim3(kBinProbeThreads), 0, st, a.ix, (const FqBinEntry *)b.ent, (const uint32_t *)b.base, (const uint32_t *)b.chunks, b.mask);
+  hipLaunchKernelGGL(k_prep_bin_verdict, dim3(nblk((uint64_t)a.n_reads, 256)), dim3(256), 0, st, a, b.mask);
+  FQ_HIP(hipEventRecord(e1, st));
+  filter_binned_reads += (uint64_t)a.n_reads;
+  return 0;
+}
 int launch_prep_packed(const FqPrepPackedArgs &a) {
   FQ_PRE();
   if (a.n_reads <= 0) return 0;
   hipEvent_t e0, e1;
   kernel_events(FQ_K_PREP_KERNEL, &e0, &e1);
   const dim3 grid(nblk((uint64_t)a.n_reads, 256));
+  // the binned form where the caller asks for it (FqPrepPackedArgs::binned), and only under the chain: its scratch is the device's
+  bool binned = a.binned && a.o.filter_thresh != 0 && !g_cur->tune.filter_no_turns && a.n_reads < FQ_BIN_MAX_READS;
   // The filter kernel is the call's one bandwidth-bound launch; beside other streams' search kernels (latency-bound, long, every CU's wave
   // slots taken) its workgroups wait for slots.  prep_priority: it goes to a stream of the highest priority, whose workgroups the dispatcher
   // places first; the call's stream waits for it.
@@ -1236,8 +1421,11 @@ int launch_prep_packed(const FqPrepPackedArgs &a) {
   if (!g_cur->tune.filter_no_turns) {   // chained per device like launch_prep
     const int dev = g_cur->device;
     std::lock_guard<std::mutex> lk(g_dev_mu);
-    if (g_prep_last[dev] && g_prep_owner[dev] != g_cur) FQ_HIP(hipStreamWaitEvent(st, g_prep_last[dev], 0));
-    hipExtLaunchKernelGGL(k_prep_packed, grid, dim3(256), 0, st, e0, e1, 0, a);
+    // (no scratch, no binned form: the direct kernel keeps the call alive; the error is the allocation's alone)
+    if (binned && bin_scratch_ensure(dev, (size_t)a.n_reads * (size_t)fq_filter_front(a.o.filter_thresh), (size_t)a.n_reads, st)) { (void)hipGetLastError(); binned = false; }
+    if (g_prep_last[dev] && (g_prep_owner[dev] != g_cur || binned)) FQ_HIP(hipStreamWaitEvent(st, g_prep_last[dev], 0));
+    if (binned) { if (launch_prep_binned(a, st, e0, e1)) return -3; }
+    else hipExtLaunchKernelGGL(k_prep_packed, grid, dim3(256), 0, st, e0, e1, 0, a);
     FQ_HIP(hipEventRecord(g_cur->prep_done, st));
     g_prep_last[dev] = g_cur->prep_done; g_prep_owner[dev] = g_cur;
     if (st != g_stream) FQ_HIP(hipStreamWaitEvent(g_stream, g_cur->prep_done, 0));

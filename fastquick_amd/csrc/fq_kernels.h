@@ -388,8 +388,10 @@ struct FqPrepPackedArgs {
   int32_t *sub_whole;      // out: [pair / batch_pairs] longest read that bwa_trim_read leaves whole (written when qual_last != NULL)
   int32_t n_pairs, batch_pairs;
   uint64_t *counters;      // FQ_C_PROBES, FQ_C_BASES (ragged), FQ_C_BADLEN (ragged)
+  int32_t binned;          // the launcher runs the binned form below (fq_align.cpp: from filter_binned_min reads a launch, under the chain of filter launches)
 };
-FQ_HD void fq_prep_packed_thread(const FqPrepPackedArgs &A, int r) {
+// What the thread does besides probing: the trimming look at the last quality byte and a ragged batch's length sums.
+FQ_HD void fq_prep_packed_lengths(const FqPrepPackedArgs &A, int r) {
   if (A.qual_last) {
     // bwa_trim_read (libbwa/bwaseqio.c:75-88) scans from the last base while the running sum of (trim_qual - q) stays >= 0: a read
     // whose last base is above the threshold (or that is shorter than 35 bases) keeps its length
@@ -416,49 +418,87 @@ FQ_HD void fq_prep_packed_thread(const FqPrepPackedArgs &A, int r) {
     FQ_ATOMIC_ADD64(&A.counters[FQ_C_BASES], (uint64_t)len);
     if (len < FQ_LMIN || len > FQ_LMAX) FQ_ATOMIC_ADD64(&A.counters[FQ_C_BADLEN], 1);
   }
+}
+// Probe q = 6 * ch + t of a read looks up the key fq_kmer_project(kmer[ch], t) in table t.  `hits` holds bit q for every probe issued up
+// front (fq_filter_front: the first 16, with thresh >= 3: an off-target read's verdict "fewer than thresh hits among 18" is certain once
+// those all miss; all 18 otherwise).  The last two are fetched here for the few reads they can decide; then the verdict with the
+// early-exit semantics of IsReadInHashByCountMoreChunck (pass as soon as the running count reaches thresh) and the probe count the
+// reference would have issued.
+FQ_HD int fq_filter_front(int thresh) { return thresh >= 3 ? 16 : 18; }
+FQ_HD uint32_t fq_filter_key(const uint64_t kmer[3], int q) { return fq_kmer_project(kmer[q / 6], q % 6); }
+FQ_HD uint8_t fq_prep_packed_verdict(const FqPrepPackedArgs &A, const uint64_t kmer[3], uint32_t hits) {
+  const int th = A.o.filter_thresh;
+  if (th >= 3 && FQ_POPC32(hits & 0xffffu) + 2 >= th)
+    for (int q = 16; q < 18; ++q) { const uint32_t x = fq_filter_key(kmer, q); hits |= (uint32_t)((A.ix.bitmap[q % 6][x >> 3] >> (x & 7u)) & 1u) << q; }
+  int cnt[3];
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) cnt[ch] = FQ_POPC32((hits >> (6 * ch)) & 63u);
+  const bool p0 = cnt[0] >= th, p1 = cnt[0] + cnt[1] >= th, p2 = cnt[0] + cnt[1] + cnt[2] >= th;
+  const uint32_t probes = p0 ? 6u : p1 ? 12u : 18u;
+#if defined(__HIP_DEVICE_COMPILE__)
+  uint32_t ps = probes;   // one atomic per wavefront
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) ps += (uint32_t)__shfl_xor((int)ps, d);
+  if (__lane_id() == (unsigned)(__ffsll((long long)__ballot(1)) - 1)) FQ_ATOMIC_ADD64(&A.counters[FQ_C_PROBES], ps);
+#else
+  FQ_ATOMIC_ADD64(&A.counters[FQ_C_PROBES], probes);
+#endif
+  return p2 ? 0 : 1;
+}
+FQ_HD void fq_prep_packed_thread(const FqPrepPackedArgs &A, int r) {
+  fq_prep_packed_lengths(A, r);
   uint8_t filt = 0;
   if (A.o.filter_thresh != 0) {
     uint64_t kmer[3];
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) kmer[ch] = A.head[(size_t)ch * (size_t)A.n_reads + (size_t)r];
-    const int th = A.o.filter_thresh;
     uint8_t byte[18];
     uint32_t bit[18], off[18];
 #pragma unroll
-    for (int ch = 0; ch < 3; ++ch)
-#pragma unroll
-      for (int t = 0; t < 6; ++t) {
-        const uint32_t x = fq_kmer_project(kmer[ch], t);
-        off[6 * ch + t] = x >> 3;
-        bit[6 * ch + t] = x & 7u;
-      }
-    // as in fq_prep_thread: 16 probes in flight, the last two only when they can change the verdict
+    for (int q = 0; q < 18; ++q) { const uint32_t x = fq_filter_key(kmer, q); off[q] = x >> 3; bit[q] = x & 7u; }
+    // as in fq_prep_thread: the probes are issued before any is consumed
 #pragma unroll
     for (int q = 0; q < 16; ++q) byte[q] = A.ix.bitmap[q % 6][off[q]];
     byte[16] = byte[17] = 0;
-    if (th < 3) { byte[16] = A.ix.bitmap[4][off[16]]; byte[17] = A.ix.bitmap[5][off[17]]; }
-    int c16 = 0;
+    if (fq_filter_front(A.o.filter_thresh) == 18) { byte[16] = A.ix.bitmap[4][off[16]]; byte[17] = A.ix.bitmap[5][off[17]]; }
+    uint32_t hits = 0;
 #pragma unroll
-    for (int q = 0; q < 16; ++q) c16 += (byte[q] >> bit[q]) & 1;
-    if (th >= 3 && c16 + 2 >= th) { byte[16] = A.ix.bitmap[4][off[16]]; byte[17] = A.ix.bitmap[5][off[17]]; }
-    int cnt[3] = {0, 0, 0};
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch)
-#pragma unroll
-      for (int t = 0; t < 6; ++t) cnt[ch] += (byte[6 * ch + t] >> bit[6 * ch + t]) & 1;
-    const bool p0 = cnt[0] >= th, p1 = cnt[0] + cnt[1] >= th, p2 = cnt[0] + cnt[1] + cnt[2] >= th;
-    filt = p2 ? 0 : 1;
-    const uint32_t probes = p0 ? 6u : p1 ? 12u : 18u;
-#if defined(__HIP_DEVICE_COMPILE__)
-    uint32_t ps = probes;   // one atomic per wavefront
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) ps += (uint32_t)__shfl_xor((int)ps, d);
-    if (__lane_id() == (unsigned)(__ffsll((long long)__ballot(1)) - 1)) FQ_ATOMIC_ADD64(&A.counters[FQ_C_PROBES], ps);
-#else
-    FQ_ATOMIC_ADD64(&A.counters[FQ_C_PROBES], probes);
-#endif
+    for (int q = 0; q < 18; ++q) hits |= (uint32_t)((byte[q] >> bit[q]) & 1u) << q;
+    filt = fq_prep_packed_verdict(A, kmer, hits);
   }
   A.filtered[r] = filt;
+}
+
+// ---- the same filter, binned: the random gather as bucket-then-probe ---------------------------------------------------------------
+// A bucket is one region of 2^24 bits (2 MiB) of one table, 6 x 256 of them: probes sorted by bucket read a region that stays in one XCD's
+// L2 instead of 3 GiB of tables.  Three phases, each a launch of its own (fq_device.hip), the same statements as host loops in tests/emu/filter_binned_check.cpp:
+//   count + offsets   entries per bucket; exclusive sums give every bucket its exact place in the entry array
+//   bin               every front probe (fq_filter_front) as an 8-byte entry {key, read << 5 | q} into the bucket of its key's top byte
+//   probe             the entries of a bucket against its region; a hit sets bit q of the read's word of the hit-mask array
+//   verdict           fq_prep_packed_lengths, fq_prep_packed_verdict over the read's word, which it leaves zero for the next launch
+// Buckets lie in the entry array by position, XCD-major: workgroups b and b + 8 share an XCD's L2 (observed placement; speed only), and
+// workgroups with blockIdx % 8 == x walk the chunks of the buckets at positions [x * FQ_BIN_PER_XCD, (x + 1) * FQ_BIN_PER_XCD) in order.
+constexpr int FQ_BIN_BUCKETS = 6 * 256, FQ_BIN_XCDS = 8, FQ_BIN_PER_XCD = FQ_BIN_BUCKETS / FQ_BIN_XCDS;
+constexpr int FQ_BIN_MAX_READS = 1 << 27;   // a read index and a probe index share an entry's second word
+struct FqBinEntry { uint32_t key, tag; };
+FQ_HD int fq_bin_pos(int q, uint32_t key) { const int b = (q % 6) * 256 + (int)(key >> 24); return (b % FQ_BIN_XCDS) * FQ_BIN_PER_XCD + b / FQ_BIN_XCDS; }
+FQ_HD FqBinEntry fq_bin_entry(uint32_t key, int r, int q) { FqBinEntry e; e.key = key; e.tag = (uint32_t)r << 5 | (uint32_t)q; return e; }
+// the region of the bucket at position p: its table's bytes from the region's first
+FQ_HD const uint8_t *fq_bin_region(const FqDevIndex &ix, int p) {
+  const int b = (p % FQ_BIN_PER_XCD) * FQ_BIN_XCDS + p / FQ_BIN_PER_XCD;
+  return ix.bitmap[b >> 8] + ((size_t)(b & 255) << 21);
+}
+FQ_HD uint32_t fq_bin_hit(const uint8_t *region, FqBinEntry e) { return (uint32_t)((region[(e.key & 0xffffffu) >> 3] >> (e.key & 7u)) & 1u); }
+FQ_HD int fq_bin_read(FqBinEntry e) { return (int)(e.tag >> 5); }
+FQ_HD uint32_t fq_bin_mask_bit(FqBinEntry e) { return 1u << (e.tag & 31u); }
+FQ_HD void fq_prep_binned_verdict_thread(const FqPrepPackedArgs &A, uint32_t *mask, int r) {
+  fq_prep_packed_lengths(A, r);
+  uint64_t kmer[3];
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) kmer[ch] = A.head[(size_t)ch * (size_t)A.n_reads + (size_t)r];
+  const uint32_t hits = mask[r];
+  if (hits) mask[r] = 0;
+  A.filtered[r] = fq_prep_packed_verdict(A, kmer, hits);
 }
 
 // ---- survivors of a packed batch: 2-bit rows -> the ASCII rows every later kernel reads --------------------------------------------

@@ -454,7 +454,8 @@ int fq_ctx_state_move(fq_ctx_t *to, fq_ctx_t *from);
 
 /* Experiment / test knobs by name (defaults are what DESIGN.md measures): gap_long_pops, gap_long_always, gap_pool,
  * gap_nogap_min, gap_pipeline_min, gap_pipeline_segs, gap_long_pops2, gap_split_hard, gap_no_order, gap_order_asc, gap_waves_per_cu, gap_coop_waves, gap_refill_min, sw_wave_max, host_threads, host_par_min, filter_no_turns,
- * refine_lanes, packed_bulk_min, trace.  FQ_EINVAL for an unknown key. */
+ * refine_lanes, packed_bulk_min, filter_binned_min (packed and text batches: reads per filter launch from which the binned form runs; 0: always, a huge value: never), trace.
+ * FQ_EINVAL for an unknown key. */
 int fq_ctx_set_tuning(fq_ctx_t *c, const char *key, int64_t value);
 
 /* ---- consumers ---------------------------------------------------------------------------
@@ -659,6 +660,8 @@ typedef struct {
   double device_wait_ms;        /* time the calls' threads slept waiting for the device (host_ms_* exclude the waits inside their sections) */
   double host_cpu_ms;           /* CPU time the calls' own threads used, set-up to result arrays (the pooled workers of the few parallel passes not included) */
   uint64_t dp_launches[FQ_DP_COUNT];   /* launches of the mate-rescue and refinement DP per kernel variant (FQ_DP_*); zero on a backend without variants */
+  uint64_t filter_binned_reads;        /* reads of packed and text batches that FQ_K_PREP filtered in the binned form (tuning key filter_binned_min) */
+  uint64_t filter_bin_spill;           /* ... entries of it that took a fallback route (the bucket offsets are counted: there is none, and this stays zero) */
 } fq_stats_t;
 void fq_stats_get(const fq_ctx_t *c, fq_stats_t *out);
 void fq_stats_reset(fq_ctx_t *c);
